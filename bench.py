@@ -13,9 +13,14 @@ HBM-resident — DESIGN.md §4).
 
 value = whole-job Σ serialized key+value bytes (the reference's
 TaskCounter.OUTPUT_BYTES semantics, PipelinedSorter.java:466) ÷ max-over-ranks
-wall time per step.  The CPU oracle (kind "port") is timed on a bounded
-sample as cpu_baseline; roofline reports the dominant kernel (radix scatter)
-against the 8 TB/s gfx950 HBM peak.
+wall time per step.  roofline reports the dominant kernel (radix scatter) of
+the last timed step against the 8 TB/s gfx950 HBM peak.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, print the result line.  --full adds the legs that take runs of
+their own: the CPU oracle (kind "port") timed on a bounded sample as
+cpu_baseline.  --dump-outputs DIR writes what the last timed step produced
+(see dump_outputs) so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -32,7 +37,7 @@ REC_SER = 4 + KLEN + 4 + VLEN  # serialized record bytes (BytesWritable k+v)
 SEED = 0x7E2C2
 
 
-def run_step_c3(tez_amd, gen_batches, free_inputs=False):
+def run_step_c3(tez_amd, gen_batches, free_inputs=False, hold=False):
     """C3: forced multi-spill + k-way merge (BASELINE configs[2]).  Each
     batch is absorbed and spilled (sorted + IFile-emitted), then flush runs
     the 32-way merge into the final output.  At the full 1e9-record size
@@ -56,15 +61,16 @@ def run_step_c3(tez_amd, gen_batches, free_inputs=False):
     t2 = time.perf_counter()
     ctr = s.counters()
     tms = s.times()
-    s.close()
+    if not hold:
+        s.close()
     tms["host_absorb_ns"] = int((t1 - t0) * 1e9)
     tms["host_flush_ns"] = int((t2 - t1) * 1e9)
     tms["host_create_ns"] = 0
     tms["host_close_ns"] = 0
-    return ctr, tms
+    return ctr, tms, ((s, [s]) if hold else None)
 
 
-def run_step_c5(tez_amd, batches):
+def run_step_c5(tez_amd, batches, hold=False):
     """C5 slice: range-partitioned (TotalOrderPartitioner-style) explicit
     placements through the C-ABI.  One batch = single spill, flush = rename;
     with --spills > 1 each batch is spilled and flush runs the
@@ -81,15 +87,17 @@ def run_step_c5(tez_amd, batches):
     t2 = time.perf_counter()
     ctr = s.counters()
     tms = s.times()
-    s.close()
+    if not hold:
+        s.close()
     tms["host_create_ns"] = 0
     tms["host_absorb_ns"] = int((t1 - t0) * 1e9)
     tms["host_flush_ns"] = int((t2 - t1) * 1e9)
     tms["host_close_ns"] = 0
-    return ctr, tms
+    return ctr, tms, ((s, [s]) if hold else None)
 
 
-def run_step_single(tez_amd, conf, d, off, kl, n, adopt=False, part=None):
+def run_step_single(tez_amd, conf, d, off, kl, n, adopt=False, part=None,
+                    hold=False):
     t0 = time.perf_counter()
     s = tez_amd.Sorter(conf)
     t1 = time.perf_counter()
@@ -102,17 +110,18 @@ def run_step_single(tez_amd, conf, d, off, kl, n, adopt=False, part=None):
     t3 = time.perf_counter()
     ctr = s.counters()
     tms = s.times()
-    s.close()
+    if not hold:
+        s.close()
     t4 = time.perf_counter()
     tms["host_create_ns"] = int((t1 - t0) * 1e9)
     tms["host_absorb_ns"] = int((t2 - t1) * 1e9)
     tms["host_flush_ns"] = int((t3 - t2) * 1e9)
     tms["host_close_ns"] = int((t4 - t3) * 1e9)
-    return ctr, tms
+    return ctr, tms, ((s, [s]) if hold else None)
 
 
 def run_step_multi(tez_amd, rank, world, device, d, off, kl, n, adopt=False,
-                   part=None, nparts=PARTS):
+                   part=None, nparts=PARTS, hold=False):
     from tez_amd import exchange as ex
     conf = tez_amd.make_conf(nparts, world_size=world, rank=rank)
     m = tez_amd.Sorter(conf)
@@ -131,9 +140,60 @@ def run_step_multi(tez_amd, rank, world, device, d, off, kl, n, adopt=False,
                           src_rec_splits=plan.recv_rec_splits,
                           src_byte_splits=plan.recv_byte_splits)
     tms = red.times()
+    if hold:
+        return ctr, tms, (red, [red, m])
     red.close()
     m.close()
-    return ctr, tms
+    return ctr, tms, None
+
+
+# --dump-outputs sample of the output stream: fixed, seeded chunk offsets
+DUMP_CHUNK = 4096
+DUMP_CHUNKS = 2048  # 8 MiB of stream bytes = 32 MiB as float32
+
+
+def dump_outputs(tez_amd, sorter, ctr, outdir, prefix=""):
+    """Write what a caller of the timed path receives from its last step as
+    outdir/<name>.npy (float32/float64, ~33 MB at the default workload):
+      index             f64 [P,3]  spill index (start_offset, raw_length,
+                                   part_length) per partition
+      counters          f64 [6]    TzsCounters in field order
+      segment_crc32     f64 [P]    each partition segment's CRC32 trailer as
+                                   emitted (covers the whole segment payload;
+                                   0 for an empty partition)
+      stream_sample_offsets f64 [K] byte offsets of the sampled chunks
+      stream_sample     f32 [K,4096] IFile stream bytes at those offsets
+    The sample is the first and the last chunk plus seeded offsets over the
+    stream, or the whole stream when it is smaller than the sample; a short
+    last chunk is zero-padded."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    dev, total, idx = sorter.output_meta()
+
+    def save(name, arr):
+        np.save(os.path.join(outdir, prefix + name + ".npy"), arr)
+
+    save("index", np.asarray(idx, dtype=np.float64).reshape(-1, 3))
+    save("counters", np.asarray(list(ctr.values()), dtype=np.float64))
+    crcs = np.zeros(len(idx), dtype=np.float64)
+    for p, (st, _raw, cl) in enumerate(idx):
+        if cl >= 4:
+            crcs[p] = int.from_bytes(tez_amd.read_device(dev, st + cl - 4, 4), "big")
+    save("segment_crc32", crcs)
+    if total <= DUMP_CHUNK * DUMP_CHUNKS:
+        offs = np.arange(0, total, DUMP_CHUNK, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(SEED)
+        offs = rng.integers(0, total - DUMP_CHUNK, size=DUMP_CHUNKS - 2,
+                            dtype=np.int64)
+        offs = np.unique(np.concatenate([offs, [0, total - DUMP_CHUNK]]))
+    sample = np.zeros((len(offs), DUMP_CHUNK), dtype=np.float32)
+    for i, o_ in enumerate(offs):
+        nb = min(DUMP_CHUNK, total - int(o_))
+        sample[i, :nb] = np.frombuffer(tez_amd.read_device(dev, int(o_), nb),
+                                       dtype=np.uint8)
+    save("stream_sample_offsets", offs.astype(np.float64))
+    save("stream_sample", sample)
 
 
 def cpu_baseline_line(sample_records=1_000_000):
@@ -191,7 +251,17 @@ def main():
                          "partitions (single-GPU slice of configs[4])")
     ap.add_argument("--spills", type=int, default=None,
                     help="forced spill count (default: 32 for c3, 1 for c5)")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own "
+                         "(cpu_baseline: the CPU oracle timed on a bounded "
+                         "sample); a plain run only sets up, warms up, times "
+                         "the steps and prints the result line")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's "
+                         "outputs as DIR/<name>.npy (spill index, counters, "
+                         "segment CRCs, seeded sample of the IFile stream)")
     ap.add_argument("--no-adopt", action="store_true",
                     help="force the copying absorb path (default: the sorter "
                          "adopts per-step pre-generated inputs zero-copy when "
@@ -333,24 +403,25 @@ def main():
             out.append((d2, off2, kl2, per))
         return out
 
-    def one_step():
+    def one_step(hold=False):
         if args.workload == "c5":
-            return run_step_c5(tez_amd, c5_batches)
+            return run_step_c5(tez_amd, c5_batches, hold=hold)
         if args.workload == "c3":
-            return run_step_c3(tez_amd, gen_batches, c3_free_inputs)
+            return run_step_c3(tez_amd, gen_batches, c3_free_inputs, hold=hold)
         if adopt:
             sd, so, sk, spart = input_sets[set_cursor[0]]
             set_cursor[0] += 1
             if use_exchange:
                 return run_step_multi(tez_amd, rank, world, device, sd, so, sk,
                                       n_local, adopt=True, part=spart,
-                                      nparts=parts_w)
+                                      nparts=parts_w, hold=hold)
             return run_step_single(tez_amd, conf, sd, so, sk, n_local, adopt=True,
-                                   part=spart)
+                                   part=spart, hold=hold)
         if use_exchange:
             return run_step_multi(tez_amd, rank, world, device, d, off, kl, n_local,
-                                  part=part, nparts=parts_w)
-        return run_step_single(tez_amd, conf, d, off, kl, n_local, part=part)
+                                  part=part, nparts=parts_w, hold=hold)
+        return run_step_single(tez_amd, conf, d, off, kl, n_local, part=part,
+                               hold=hold)
 
     last_ctr = last_tms = None
     if c3_free_inputs and args.steps > 1:
@@ -358,15 +429,31 @@ def main():
               flush=True)
         args.steps = 1
     for _ in range(args.warmup):
-        last_ctr, last_tms = one_step()
+        last_ctr, last_tms, _held = one_step()
         if c3_free_inputs:
             gen_batches = regen_c3()   # untimed regeneration (pool-backed)
     barrier_sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last_ctr, last_tms = one_step()
+    held = None
+    for k in range(args.steps):
+        # --dump-outputs: the last step's sorters stay open past the timed
+        # region so their output can be read back; their close is timed
+        # below and counted, so the step means what it does without a dump
+        last_ctr, last_tms, held = one_step(
+            hold=bool(args.dump_outputs) and k == args.steps - 1)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    if held:
+        out_sorter, to_close = held
+        dump_outputs(tez_amd, out_sorter, last_ctr, args.dump_outputs,
+                     prefix=f"rank{rank}_" if world > 1 else "")
+        tc = time.perf_counter()
+        for srt in to_close:
+            srt.close()
+        dt_close = time.perf_counter() - tc
+        elapsed += dt_close
+        if "host_close_ns" in last_tms:
+            last_tms["host_close_ns"] += int(dt_close * 1e9)
     if dist:
         import torch
         t = torch.tensor([elapsed], device=device)
@@ -407,7 +494,8 @@ def main():
                         and world == 1 else None),
         }
         cpu = None
-        if not args.skip_cpu_baseline and world == 1 and args.workload == "c2":
+        if (args.full and not args.skip_cpu_baseline and world == 1
+                and args.workload == "c2"):
             cpu = cpu_baseline_line()
         out = {
             "metric": "shuffled+sorted KV bytes/sec",

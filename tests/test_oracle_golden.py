@@ -9,24 +9,20 @@ the codec: IFile.java:352-368), the known length accounting, and the oracle's
 record-framing parser (vints, RLE markers, EOF) on the decompressed payload
 with Text keys + IntWritable values.
 
-The fixture is read from /root/reference in THIS container only; a
-repo-committed copy of the derived per-segment payloads is NOT needed because
-this test is CPU-only and skipped where the reference tree is absent.
+The fixture is a data file the reference's own test reads; a copy is stored
+under tests/golden/ so the test is self-contained.
 """
 import os
 import zlib
 
-import pytest
-
 import oracle as o
 
-FIXTURE = ("/root/reference/tez-runtime-library/src/test/resources/"
-           "TestIFile_concatenated_compressed.bin")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                       "TestIFile_concatenated_compressed.bin")
 RAWS = [2392, 102314, 42576, 31432, 25090]
 COMPRESSED = [723, 25396, 10926, 8203, 6665]
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference tree absent")
 def test_golden_concatenated_zlib():
     blob = open(FIXTURE, "rb").read()
     assert len(blob) == sum(COMPRESSED)
