@@ -365,6 +365,81 @@ __global__ void k_build_composite2(RecTable rt, const int32_t* d_part, int32_t P
   }
 }
 
+/* Streamed content-mode composite for one contiguous buffer of uniform
+ * records (rec_u % 4 == 0, rec_u <= 128, data0 16-byte aligned, BYTES keys):
+ * a wave owns 64 consecutive records = one aligned run of 64*rec_u bytes,
+ * loads it with coalesced 16-byte loads (all issued before any use) into a
+ * wave-private LDS region, and lane r then reads the content words of
+ * record r from LDS.  Same arithmetic as d_hash_bytes / d_composite_one
+ * with ser_mode == 0.  k_build_composite2 has each lane gather its own
+ * record: 64 cache lines per load instruction for 1-16 useful bytes. */
+template <int NV /* 16-byte loads per lane = ceil(rec_u / 16) */>
+__global__ __launch_bounds__(BLOCK) void k_build_composite_stream(
+    const uint8_t* __restrict__ data0, const int32_t* __restrict__ d_part,
+    int32_t P, int pbits, int sort_bytes, uint32_t rec_u,
+    uint32_t clen /* key content bytes = klen_u - 4 */,
+    uint64_t* __restrict__ d_key, uint32_t* __restrict__ d_idx, uint32_t n) {
+  extern __shared__ uint4 cs_lds[]; /* BLOCK/WAVE regions of NV KiB */
+  const uint32_t W = rec_u >> 2;
+  const uint32_t nvec = 16 * W;     /* uint4s in a full 64-record run */
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wib = threadIdx.x / WAVE;
+  uint4* L4 = cs_lds + wib * (NV * WAVE);
+  const uint32_t* mine = (const uint32_t*)L4 + lane * W + 1; /* content */
+  const uint64_t mask = (sort_bytes >= 8) ? ~0ull : ~0ull << (8 * (8 - sort_bytes));
+  /* words the lane needs: all content for the hash, 8 bytes otherwise */
+  const uint32_t cbytes = d_part ? (clen < 8 ? clen : 8) : clen;
+  const uint32_t nw = (cbytes + 3) >> 2;
+  const uint64_t ngroups = ((uint64_t)n + WAVE - 1) / WAVE;
+  const uint32_t nwaves = gridDim.x * (BLOCK / WAVE);
+  for (uint64_t g = blockIdx.x * (BLOCK / WAVE) + wib; g < ngroups; g += nwaves) {
+    const uint64_t base = g * WAVE;
+    const uint64_t i = base + lane;
+    int32_t h = 1;
+    uint64_t c = 0;
+    if (base + WAVE <= n) {
+      const uint4* src = (const uint4*)(data0 + base * rec_u);
+      /* NV = ceil(W/4) loads per lane; only the last can run past the run.
+         There the source index is clamped and the (repeated) value still
+         written, into the slack of the NV KiB region: a predicate would
+         make the compiler branch around each load and wait for it alone */
+      uint4 v[NV];
+#pragma unroll
+      for (int j = 0; j < NV; j++) {
+        uint32_t t = j * WAVE + lane;
+        v[j] = src[(j < NV - 1 || t < nvec) ? t : nvec - 1];
+      }
+#pragma unroll
+      for (int j = 0; j < NV; j++) L4[j * WAVE + lane] = v[j];
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t j = 0; j < nw; j++) {
+        uint32_t x = mine[j];
+        uint32_t nb = cbytes - 4 * j < 4 ? cbytes - 4 * j : 4;
+        if (!d_part)
+          for (uint32_t b = 0; b < nb; b++)
+            h = (int32_t)((uint32_t)h * 31u) + (int8_t)(uint8_t)(x >> (8 * b));
+        if (j < 2) {
+          if (nb < 4) x &= (1u << (8 * nb)) - 1u;
+          c |= (uint64_t)__builtin_bswap32(x) << (32 * (1 - j));
+        }
+      }
+      __builtin_amdgcn_wave_barrier(); /* reads done before the next fill */
+    } else if (i < n) {
+      const uint8_t* ct = data0 + i * rec_u + 4;
+      if (!d_part) h = d_hash_bytes(ct, (int32_t)clen);
+      uint32_t m = clen < 8 ? clen : 8;
+      for (uint32_t b = 0; b < m; b++) c |= (uint64_t)ct[b] << (56 - 8 * b);
+    }
+    if (i < n) {
+      uint32_t part = d_part ? (uint32_t)d_part[i]
+                             : (uint32_t)((h & 0x7fffffff) % P);
+      uint64_t key = pbits ? (((uint64_t)part << (64 - pbits)) | (c >> pbits)) : c;
+      d_key[i] = key & mask;
+      d_idx[i] = (uint32_t)i;
+    }
+  }
+}
+
 __global__ void k_build_composite(RecTable rt, const int32_t* d_part, int32_t P,
                                   int pbits, int ref_pb, int sort_bytes, int ser_mode,
                                   uint64_t* d_key, uint32_t* d_idx, uint32_t n) {
@@ -3631,6 +3706,18 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
                            SpillData* outsp, bool apply_combine,
                            SpillData* retain, const uint64_t* d_lo);
 
+/* Gate of k_build_composite_stream: one contiguous, 16-byte aligned buffer
+ * of uniform BYTES-key records of rec_u/4 <= 32 whole dwords.
+ * TZS_STREAM_UNIFORM=0 selects k_build_composite2 instead; it is read on
+ * every sort (not cached) so a test can flip it in-process. */
+static bool stream_uniform_gate(const RecTable& rt) {
+  const char* e = getenv("TZS_STREAM_UNIFORM");
+  if (e && e[0] == '0') return false;
+  return rt.nspills == 1 && rt.key_type == 0 && rt.rec_u0 != 0 &&
+         rt.klen_u0 >= 4 && rt.klen_u0 <= rt.rec_u0 && rt.rec_u0 % 4 == 0 &&
+         rt.rec_u0 <= 128 && ((uintptr_t)rt.data0 & 15) == 0;
+}
+
 /* ---- the core: sort current buffer + emit IFile segments ---- */
 static int sort_and_emit(tzs_sorter* s, HostRT& hrt, uint32_t n,
                          const int32_t* d_part_unsorted,
@@ -3653,9 +3740,23 @@ static int sort_and_emit(tzs_sorter* s, HostRT& hrt, uint32_t n,
   if (s->sidx.alloc(sizeof(uint32_t) * n)) return -12;
   uint64_t* d_key = (uint64_t*)s->skey.p;
   uint32_t* d_idx = (uint32_t*)s->sidx.p;
-  hipLaunchKernelGGL(k_build_composite2, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
-                     d_part_unsorted, P, pbits, prm.ref_pb, SB, ser_mode, d_key,
-                     d_idx, n);
+  if (ser_mode == 0 && stream_uniform_gate(rt)) {
+#define TZS_CS_LAUNCH(NV)                                                     \
+  case NV:                                                                    \
+    hipLaunchKernelGGL((k_build_composite_stream<NV>), dim3(grid1d(n)),       \
+                       dim3(BLOCK), (BLOCK / WAVE) * NV * WAVE * 16, 0,       \
+                       rt.data0, d_part_unsorted, P, pbits, SB, rt.rec_u0,    \
+                       rt.klen_u0 - 4, d_key, d_idx, n);                      \
+    break;
+    switch ((rt.rec_u0 + 15) / 16) {
+      TZS_CS_LAUNCH(1) TZS_CS_LAUNCH(2) TZS_CS_LAUNCH(3) TZS_CS_LAUNCH(4)
+      TZS_CS_LAUNCH(5) TZS_CS_LAUNCH(6) TZS_CS_LAUNCH(7) TZS_CS_LAUNCH(8)
+    }
+#undef TZS_CS_LAUNCH
+  } else
+    hipLaunchKernelGGL(k_build_composite2, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
+                       d_part_unsorted, P, pbits, prm.ref_pb, SB, ser_mode, d_key,
+                       d_idx, n);
   (void)hipEventRecord(ev[1]);
 
   /* 2. base radix sort over the top SB bytes of the composite */
