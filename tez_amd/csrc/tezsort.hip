@@ -1034,6 +1034,117 @@ __global__ void k_eq_init(const uint64_t* skeys, uint8_t* eq, int pbits,
     parts[i] = pbits ? (uint32_t)(k >> (64 - pbits)) : 0;
   }
 }
+/* One pass over the sorted composites for everything the host and the
+ * refinement need before the first level: eq + parts exactly as
+ * k_eq_init/k_eq_init2 write them (lo == NULL: composites only), plus
+ *   meta[0]        += number of set eq flags (one atomic per block)
+ *   meta[1 + q]     = first sorted position of partition q, q in [0, P];
+ *                     meta[1 + P] = n.  No atomics: in sorted order the
+ *                     position where part(i) != part(i-1) owns every q in
+ *                     (part(i-1), part(i)], position 0 owns [0, part(0)] and
+ *                     position n-1 also owns (part(n-1), P], so empty
+ *                     partitions anywhere get a start too.
+ *   tile_inrun[t]   = positions of SCAN_TILE tile t with eq[i] || eq[i+1]
+ *                     (k_refine_compact_lb skips tiles where this is 0).
+ * A block owns one tile; a thread owns SCAN_ITEMS consecutive positions and
+ * loads them once plus one neighbour on each side.  meta must be zeroed
+ * before the launch (n == 0 then leaves every start at 0). */
+__global__ __launch_bounds__(BLOCK) void k_post_sort_meta(
+    const uint64_t* skeys, const uint64_t* lo, uint8_t* eq, int pbits,
+    uint32_t* parts, uint32_t n, int P, uint32_t* meta, uint32_t* tile_inrun) {
+  __shared__ uint32_t wred[WPB];
+  const uint32_t tile = blockIdx.x;
+  const uint64_t i0 = (uint64_t)tile * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wv = threadIdx.x / WAVE;
+  uint32_t cnt = 0; /* (inrun << 16) | neq, each <= SCAN_TILE */
+  if (i0 < n) {
+    const uint32_t m = (uint32_t)min((uint64_t)SCAN_ITEMS, (uint64_t)n - i0);
+    /* k[0] = left neighbour, k[1..8] = own span, k[9] = right neighbour */
+    uint64_t k[SCAN_ITEMS + 2], l[SCAN_ITEMS + 2];
+    #pragma unroll
+    for (int j = 0; j < SCAN_ITEMS + 2; j++) { k[j] = 0; l[j] = 0; }
+    if (m == SCAN_ITEMS) {
+      const ulonglong2* kp = (const ulonglong2*)(skeys + i0);
+      #pragma unroll
+      for (int j = 0; j < SCAN_ITEMS / 2; j++) {
+        ulonglong2 t = kp[j];
+        k[1 + 2 * j] = t.x; k[2 + 2 * j] = t.y;
+      }
+      if (lo) {
+        const ulonglong2* lp = (const ulonglong2*)(lo + i0);
+        #pragma unroll
+        for (int j = 0; j < SCAN_ITEMS / 2; j++) {
+          ulonglong2 t = lp[j];
+          l[1 + 2 * j] = t.x; l[2 + 2 * j] = t.y;
+        }
+      }
+    } else {
+      #pragma unroll
+      for (int j = 0; j < SCAN_ITEMS; j++)
+        if ((uint32_t)j < m) {
+          k[1 + j] = skeys[i0 + j];
+          if (lo) l[1 + j] = lo[i0 + j];
+        }
+    }
+    const bool has_prev = i0 > 0;
+    const bool has_next = i0 + SCAN_ITEMS < n; /* implies m == SCAN_ITEMS */
+    if (has_prev) { k[0] = skeys[i0 - 1]; if (lo) l[0] = lo[i0 - 1]; }
+    if (has_next) {
+      k[SCAN_ITEMS + 1] = skeys[i0 + SCAN_ITEMS];
+      if (lo) l[SCAN_ITEMS + 1] = lo[i0 + SCAN_ITEMS];
+    }
+    /* e[j] = eq flag of position i0 + j; e[SCAN_ITEMS] is the lookahead */
+    uint8_t e[SCAN_ITEMS + 1];
+    uint32_t pr[SCAN_ITEMS];
+    #pragma unroll
+    for (int j = 0; j <= SCAN_ITEMS; j++) {
+      bool valid = (j < SCAN_ITEMS) ? ((uint32_t)j < m && (j > 0 || has_prev))
+                                    : has_next;
+      e[j] = (valid && k[1 + j] == k[j] && l[1 + j] == l[j]) ? 1 : 0;
+    }
+    #pragma unroll
+    for (int j = 0; j < SCAN_ITEMS; j++)
+      pr[j] = pbits ? (uint32_t)(k[1 + j] >> (64 - pbits)) : 0;
+    if (m == SCAN_ITEMS) {
+      uint64_t w = 0;
+      #pragma unroll
+      for (int j = 0; j < SCAN_ITEMS; j++) w |= (uint64_t)e[j] << (8 * j);
+      *(uint64_t*)(eq + i0) = w;
+      uint4* pp = (uint4*)(parts + i0);
+      pp[0] = make_uint4(pr[0], pr[1], pr[2], pr[3]);
+      pp[1] = make_uint4(pr[4], pr[5], pr[6], pr[7]);
+    } else {
+      #pragma unroll
+      for (int j = 0; j < SCAN_ITEMS; j++)
+        if ((uint32_t)j < m) { eq[i0 + j] = e[j]; parts[i0 + j] = pr[j]; }
+    }
+    #pragma unroll
+    for (int j = 0; j < SCAN_ITEMS; j++)
+      if ((uint32_t)j < m) {
+        cnt += (uint32_t)e[j] + ((uint32_t)(e[j] | e[j + 1]) << 16);
+        /* partition starts owned by this position (loops bounded by P) */
+        int64_t pprev = (j > 0 || has_prev)
+            ? (int64_t)(pbits ? (uint32_t)(k[j] >> (64 - pbits)) : 0) : -1;
+        int64_t pcur = pr[j];
+        if (pcur != pprev)
+          for (int64_t q = pprev + 1; q <= pcur && q <= P; q++)
+            meta[1 + q] = (uint32_t)(i0 + j);
+        if (i0 + j == (uint64_t)n - 1)
+          for (int64_t q = pcur + 1; q <= P; q++) meta[1 + q] = n;
+      }
+  }
+  #pragma unroll
+  for (int s2 = WAVE / 2; s2 >= 1; s2 >>= 1) cnt += __shfl_xor(cnt, s2, WAVE);
+  if (lane == 0) wred[wv] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int w = 0; w < WPB; w++) tot += wred[w];
+    if (tot & 0xFFFFu) atomicAdd(meta, tot & 0xFFFFu);
+    tile_inrun[tile] = tot >> 16;
+  }
+}
 /* inrun[i] = eq[i] || eq[i+1]; runstart[i] = inrun && !eq[i].
  * Both 0/1 flags ride ONE u64 as (inrun << 32) | runstart so a single
  * scan_u64 produces both prefix sums — each field's total is <= n <= 2^32-1
@@ -1113,11 +1224,46 @@ __global__ void k_compact_refine(RecTable rt, const uint32_t* sidx,
  * scratch traffic; C3's refinement was the dominant profile block).
  * Packed u64 counters: (inrun << 32) | runstart, same protocol as
  * k_scan_lookback. */
+/* One thread publishes its tile's aggregate and resolves the tile's
+ * exclusive prefix by look-back (tile 0: inclusive at once).  Every tile
+ * that took a ticket must come through here exactly once, whether it has
+ * anything to compact or not: a tile that never reaches OSS_INC leaves
+ * every later tile spinning to the timeout. */
+__device__ __forceinline__ uint64_t d_oss_publish_lookback(
+    uint64_t* status, uint32_t tile, uint64_t block_total, uint32_t* error) {
+  if (tile == 0) {
+    __hip_atomic_store((os_gu64*)&status[0], OSS_INC | block_total,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return 0;
+  }
+  __hip_atomic_store((os_gu64*)&status[tile], OSS_AGG | block_total,
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  uint64_t e = 0;
+  int64_t p = (int64_t)tile - 1;
+  uint32_t spins = 0;
+  while (p >= 0) {
+    uint64_t v = __hip_atomic_load((os_gu64*)&status[p],
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v & OSS_INC) { e += v & OSS_VAL; break; }
+    if (v & OSS_AGG) { e += v & OSS_VAL; p--; continue; }
+    if (++spins > 100000000u) { atomicAdd(error, 1u); break; }
+    __builtin_amdgcn_s_sleep(4);
+  }
+  __hip_atomic_store((os_gu64*)&status[tile], OSS_INC | (e + block_total),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return e;
+}
+/* tile_inrun (nullable): per-tile in-run counts from k_post_sort_meta at
+ * level 0.  eq flags are only ever cleared after that (k_eq_update), so a
+ * zero there stays a proof that the tile has nothing to compact at every
+ * later level: such a tile publishes a zero aggregate and returns without
+ * reading eq or sidx. */
 __global__ __launch_bounds__(BLOCK) void k_refine_compact_lb(
     RecTable rt, const uint32_t* sidx, const uint8_t* eq, uint32_t n,
     int level_byte0, int use_len_level, int ser_mode, const uint64_t* lk0,
     uint64_t* lkey, uint32_t* seg, uint32_t* pos,
-    uint64_t* status, uint32_t* ticket, uint32_t* error, uint64_t* total_out) {
+    uint64_t* status, uint32_t* ticket, uint32_t* error, uint64_t* total_out,
+    const uint32_t* tile_inrun) {
   __shared__ uint64_t wsum[WPB + 1];
   __shared__ uint32_t s_tile;
   __shared__ uint64_t s_excl;
@@ -1125,6 +1271,13 @@ __global__ __launch_bounds__(BLOCK) void k_refine_compact_lb(
   __syncthreads();
   const uint32_t tile = s_tile;
   const uint32_t base = tile * SCAN_TILE;
+  if (tile_inrun && tile_inrun[tile] == 0) { /* block-uniform */
+    if (threadIdx.x == 0) {
+      uint64_t e = d_oss_publish_lookback(status, tile, 0, error);
+      if (total_out && (uint64_t)base + SCAN_TILE >= n) *total_out = e;
+    }
+    return;
+  }
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = threadIdx.x / WAVE;
   uint8_t my_eq[SCAN_ITEMS];
@@ -1173,30 +1326,8 @@ __global__ __launch_bounds__(BLOCK) void k_refine_compact_lb(
   __syncthreads();
   uint64_t my_incl = wsum[wv] + inc;
   uint64_t block_total = wsum[WPB];
-  if (threadIdx.x == 0) {
-    if (tile == 0) {
-      __hip_atomic_store((os_gu64*)&status[0], OSS_INC | block_total,
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_excl = 0;
-    } else {
-      __hip_atomic_store((os_gu64*)&status[tile], OSS_AGG | block_total,
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      uint64_t e = 0;
-      int64_t p = (int64_t)tile - 1;
-      uint32_t spins = 0;
-      while (p >= 0) {
-        uint64_t v = __hip_atomic_load((os_gu64*)&status[p],
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v & OSS_INC) { e += v & OSS_VAL; break; }
-        if (v & OSS_AGG) { e += v & OSS_VAL; p--; continue; }
-        if (++spins > 100000000u) { atomicAdd(error, 1u); break; }
-        __builtin_amdgcn_s_sleep(4);
-      }
-      __hip_atomic_store((os_gu64*)&status[tile], OSS_INC | (e + block_total),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_excl = e;
-    }
-  }
+  if (threadIdx.x == 0)
+    s_excl = d_oss_publish_lookback(status, tile, block_total, error);
   __syncthreads();
   uint64_t excl = s_excl + my_incl - sum;
   /* prefetch the dense-key gathers for all 8 elements up front (the
@@ -2109,18 +2240,29 @@ __global__ void k_permute_records(RecTable rt, const uint32_t* sidx,
 
 /* ---- CRC over emitted segments ----
  * chunk kernel: thread computes CRC32 of one 256-byte chunk of one partition's
- * checksummed range (payload .. EOF); combine kernel: one wave per partition
- * reduces its chunk list sequentially with the 256-byte shift matrix. */
+ * checksummed range (payload .. EOF) and each wave folds its 16 chunks into
+ * one CRC per 4 KiB unit; combine kernel: one block per partition folds its
+ * unit list (thread-serial spans, then an LDS tree). */
 #define CRC_CHUNK 256
 __constant__ uint32_t c_crc_table[256];
 __constant__ uint32_t c_crc_table8[8][256]; /* slice-by-8: T0 = standard */
 __constant__ uint32_t c_crc_mats[CRC_MATS][32];
-/* byte-sliced SHIFT operators (multiply by x^(8*64) / x^(8*256)):
+/* byte-sliced SHIFT operators (multiply by x^(8*N)):
  * shiftN(crc) = T[0][crc&FF] ^ T[1][crc>>8 &FF] ^ T[2][..] ^ T[3][crc>>24]
  * — 4 table lookups instead of a 32-step serial GF(2) matrix apply. */
-__constant__ uint32_t c_crc_t64[4][256];
-__constant__ uint32_t c_crc_t256[4][256];
+__constant__ uint32_t c_crc_t64[4][256]; /* N = 64 */
+__constant__ uint32_t c_crc_t4k[4][256]; /* N = 4096, one 4 KiB unit */
+/* shift by 256 * d bytes, d = 0..15, sliced by NIBBLE (8 lookups, 512 B per
+ * operator): k_crc_chunks keeps all sixteen in LDS next to its 12 KB of
+ * data tables and stays at 8 waves/SIMD */
+__constant__ uint32_t c_crc_tn[16][8][16];
 
+__device__ __forceinline__ uint32_t d_crc_shift_nib(const uint32_t (*t)[16], uint32_t v) {
+  uint32_t r = 0;
+  #pragma unroll
+  for (int j = 0; j < 8; j++) r ^= t[j][(v >> (4 * j)) & 15];
+  return r;
+}
 __device__ __forceinline__ uint32_t d_crc_shift(uint32_t crc, uint64_t nbytes) {
   for (int k = 0; nbytes; k++, nbytes >>= 1)
     if (nbytes & 1) {
@@ -2148,19 +2290,34 @@ __device__ __forceinline__ uint32_t d_crc_shift(uint32_t crc, uint64_t nbytes) {
  * shuffle-gathered quarter CRCs merge with the byte-sliced shift-by-64
  * operator.  No data staging, no per-iteration barriers — the old LDS-staged
  * version was 84% wave-parked (PMC, profiles/) on the load->sync->compute
- * serialization. */
+ * serialization.
+ * Each wave then folds its 16 finalised chunk CRCs, in order, into ONE CRC
+ * per CRC_UNIT_BYTES (4 KiB, a quarter super-chunk); combine(L,R) =
+ * shift(L, len_R) ^ R is associative, not commutative.  In a full unit
+ * chunk i is shifted once by the fixed 256 * (15 - i) bytes (nibble-sliced
+ * tables) and the results are XORed; the ragged last unit of a range takes
+ * a shuffle tree with the length-aware d_crc_shift on the true remaining
+ * lengths.  The waves of a block never meet (no barrier in the loop).
+ * Units tile a range without gaps (16384 = 4 * 4096), so
+ * k_crc_combine_ranges sees a plain sequence of 4 KiB units of which only
+ * the last can be short. */
+#define CRC_UNIT_BYTES (CRC_SC_BYTES / WPB)
 __global__ __launch_bounds__(BLOCK) void k_crc_chunks(
     const uint8_t* stream, const uint64_t* range_start, const uint64_t* range_len,
-    const uint64_t* chunk_base, const uint64_t* sc_base /* [P+1] */,
-    uint32_t nparts, uint32_t total_sc, uint32_t* chunk_crc) {
+    const uint64_t* sc_base /* [P+1] */,
+    uint32_t nparts, uint32_t total_sc, uint32_t* unit_crc /* [WPB * total_sc] */) {
   __shared__ uint32_t tab8[8][256];
   __shared__ uint32_t t64[4][256];
+  __shared__ uint32_t tn[16][8][16]; /* shift by 256 * d bytes, d = 0..15 */
   for (int i = threadIdx.x; i < 2048; i += blockDim.x)
     ((uint32_t*)tab8)[i] = ((const uint32_t*)c_crc_table8)[i];
   for (int i = threadIdx.x; i < 1024; i += blockDim.x)
     ((uint32_t*)t64)[i] = ((const uint32_t*)c_crc_t64)[i];
+  for (int i = threadIdx.x; i < 16 * 8 * 16; i += blockDim.x)
+    ((uint32_t*)tn)[i] = ((const uint32_t*)c_crc_tn)[i];
   __syncthreads();
   const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = threadIdx.x / WAVE;
   for (uint32_t sc = blockIdx.x; sc < total_sc; sc += gridDim.x) {
     uint32_t lo = 0, hi = nparts;
     while (lo + 1 < hi) {
@@ -2230,101 +2387,113 @@ __global__ __launch_bounds__(BLOCK) void k_crc_chunks(
           crc ^= vs[q];
         }
       }
-      chunk_crc[chunk_base[p] + sc_local * CRC_SC_CHUNKS + chunk] = crc ^ 0xFFFFFFFFu;
     }
+    /* v/vl: finalised CRC and byte length of the span this lane heads
+       (chunk lanes only; a dead chunk is the empty span: crc 0, len 0) */
+    const bool full = avail >= (uint64_t)(wv + 1) * CRC_UNIT_BYTES; /* wave-uniform */
+    uint32_t v = (live && quarter == 0) ? (crc ^ 0xFFFFFFFFu) : 0u;
+    if (full) {
+      /* shift is linear, so the in-order fold of 16 full chunks equals the
+         XOR of every chunk CRC shifted once by the bytes that follow it in
+         the unit: one table apply per chunk lane, then a plain XOR
+         reduction (the other lanes hold 0) */
+      const uint32_t ci = (lane >> 2) & 15;
+      if (quarter == 0) v = d_crc_shift_nib(tn[15 - ci], v);
+      #pragma unroll
+      for (int m = 4; m < WAVE; m <<= 1) v ^= __shfl_xor(v, m, WAVE);
+    } else {
+      /* short last unit: shuffle tree over adjacent spans, true lengths */
+      uint32_t vl = (quarter == 0) ? (uint32_t)len : 0u;
+      #pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t step = 4u << j; /* lanes between adjacent spans */
+        uint32_t rv = __shfl(v, (lane + step) & (WAVE - 1));
+        uint32_t rl = __shfl(vl, (lane + step) & (WAVE - 1));
+        if ((lane & (2 * step - 1)) == 0) {
+          if (rl) v = d_crc_shift(v, rl) ^ rv;
+          vl += rl;
+        }
+      }
+    }
+    /* a wave wholly past the end of the range has no unit */
+    if (lane == 0 && avail > (uint64_t)wv * CRC_UNIT_BYTES)
+      unit_crc[(uint64_t)sc * WPB + wv] = v;
   }
 }
 
-/* Tree combine, two levels: thread-serial fold of 8 chunks, then an LDS tree
- * over ADJACENT spans; a final kernel folds each partition's groups.  Every
- * fold is combine(L,R) = shift(crc_L, len_R) ^ crc_R with the generic
- * bit-decomposed shift so ragged tails are exact. */
-#define CRC_GROUP_CHUNKS 2048
-__global__ void k_crc_combine_groups(const uint64_t* range_len, const uint64_t* chunk_base,
-                                     const uint64_t* group_base /* [P+1] */,
-                                     const uint32_t* chunk_crc, uint32_t nparts,
-                                     uint32_t total_groups,
-                                     uint32_t* group_crc, uint64_t* group_len) {
+/* d_crc_shift over an LDS copy of the shift matrices, one matrix apply fully
+ * unrolled (32 independent lookups): the constant-memory form walks the set
+ * bits with one dependent load each. */
+__device__ __forceinline__ uint32_t d_crc_shift_lds(const uint32_t (*m)[32],
+                                                    uint32_t crc, uint64_t nbytes) {
+  for (int k = 0; nbytes; k++, nbytes >>= 1)
+    if (nbytes & 1) {
+      uint32_t s = 0;
+      #pragma unroll
+      for (int i = 0; i < 32; i++) s ^= ((crc >> i) & 1) ? m[k][i] : 0u;
+      crc = s;
+    }
+  return crc;
+}
+
+/* Range combine: one block per range folds the range's 4 KiB unit CRCs
+ * (k_crc_chunks; unit u of range p sits at WPB * sc_base[p] + u) into
+ * part_crc[p].  Each thread folds a contiguous span of `per` units serially
+ * with the shift-by-4096 table (only the last unit of a range can be short:
+ * length-aware shift), then an LDS tree merges ADJACENT spans with their
+ * true byte lengths -- CRC combine is associative but not commutative.  per
+ * is a power of two, so every tree shift except the ones that absorb the
+ * short tail is a single matrix apply.  Empty ranges give 0; threads past
+ * the range hold the empty span. */
+__global__ __launch_bounds__(BLOCK) void k_crc_combine_ranges(
+    const uint64_t* range_len, const uint64_t* sc_base /* [P+1] */,
+    const uint32_t* unit_crc, uint32_t* part_crc) {
   __shared__ uint32_t s_crc[BLOCK];
   __shared__ uint64_t s_len[BLOCK];
-  __shared__ uint32_t t256[4][256];
+  __shared__ uint32_t t4k[4][256];
+  __shared__ uint32_t mats[CRC_MATS][32];
   for (int i = threadIdx.x; i < 1024; i += blockDim.x)
-    ((uint32_t*)t256)[i] = ((const uint32_t*)c_crc_t256)[i];
+    ((uint32_t*)t4k)[i] = ((const uint32_t*)c_crc_t4k)[i];
+  for (int i = threadIdx.x; i < CRC_MATS * 32; i += blockDim.x)
+    ((uint32_t*)mats)[i] = ((const uint32_t*)c_crc_mats)[i];
   __syncthreads();
-  for (uint32_t g = blockIdx.x; g < total_groups; g += gridDim.x) {
-    /* find partition via binary search over group_base */
-    uint32_t lo = 0, hi = nparts;
-    while (lo + 1 < hi) {
-      uint32_t mid = (lo + hi) / 2;
-      if (group_base[mid] <= g) lo = mid; else hi = mid;
-    }
-    uint32_t p = lo;
-    uint64_t glocal = g - group_base[p];
-    uint64_t len = range_len[p];
-    uint64_t nchunks = (len + CRC_CHUNK - 1) / CRC_CHUNK;
-    uint64_t c0 = glocal * CRC_GROUP_CHUNKS;
-    uint64_t cend = min(c0 + (uint64_t)CRC_GROUP_CHUNKS, nchunks);
-    /* thread-serial fold of 8 consecutive chunks */
-    uint64_t t0 = c0 + (uint64_t)threadIdx.x * 8;
-    uint32_t crc = 0;
-    uint64_t mylen = 0;
-    for (uint64_t c = t0; c < min(t0 + 8, cend); c++) {
-      uint64_t clen = len - c * CRC_CHUNK;
-      if (clen > CRC_CHUNK) clen = CRC_CHUNK;
-      if (clen == CRC_CHUNK)
-        crc = t256[0][crc & 0xFF] ^ t256[1][(crc >> 8) & 0xFF]
-            ^ t256[2][(crc >> 16) & 0xFF] ^ t256[3][crc >> 24]
-            ^ chunk_crc[chunk_base[p] + c];
-      else
-        crc = d_crc_shift(crc, clen) ^ chunk_crc[chunk_base[p] + c];
-      mylen += clen;
-    }
-    s_crc[threadIdx.x] = crc;
-    s_len[threadIdx.x] = mylen;
-    __syncthreads();
-    /* LDS tree over ADJACENT spans: CRC combine is associative but NOT
-     * commutative, so thread t merges [t, t+stride) with [t+stride, t+2s). */
-    for (int stride = 1; stride < BLOCK; stride <<= 1) {
-      if ((threadIdx.x & (2 * stride - 1)) == 0 && threadIdx.x + stride < BLOCK) {
-        uint64_t rl = s_len[threadIdx.x + stride];
-        if (rl) {
-          s_crc[threadIdx.x] = d_crc_shift(s_crc[threadIdx.x], rl)
-                               ^ s_crc[threadIdx.x + stride];
-          s_len[threadIdx.x] += rl;
-        }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) { group_crc[g] = s_crc[0]; group_len[g] = s_len[0]; }
-    __syncthreads();
-  }
-}
-__global__ void k_crc_combine_final(const uint64_t* group_base, const uint32_t* group_crc,
-                                    const uint64_t* group_len, uint32_t nparts,
-                                    uint32_t* part_crc) {
-  /* one WAVE per partition; each GF(2) matrix application is lane-parallel:
-   * lane i contributes mats[k][i] when bit i of the crc is set, then a
-   * butterfly XOR-reduces across the wave (6 steps instead of a 32-step
-   * serial fold per shift). */
-  uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  uint32_t lane = threadIdx.x & (WAVE - 1);
-  if (wave >= nparts) return;
-  uint32_t p = wave;
+  const uint32_t p = blockIdx.x;
+  const uint64_t len = range_len[p];
+  const uint64_t u0 = sc_base[p] * WPB;
+  const uint64_t nu = (len + CRC_UNIT_BYTES - 1) / CRC_UNIT_BYTES;
+  uint64_t per = 1;
+  while (per * BLOCK < nu) per <<= 1;
+  const uint64_t t0 = (uint64_t)threadIdx.x * per;
+  const uint64_t t1 = min(t0 + per, nu);
   uint32_t crc = 0;
-  for (uint64_t g = group_base[p]; g < group_base[p + 1]; g++) {
-    uint64_t nb = group_len[g];
-    if (!nb) continue;
-    for (int k = 0; nb; k++, nb >>= 1) {
-      if (nb & 1) {
-        uint32_t contrib = (lane < 32 && ((crc >> lane) & 1)) ? c_crc_mats[k][lane] : 0;
-        #pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) contrib ^= __shfl_xor(contrib, s, WAVE);
-        crc = contrib;
+  uint64_t mylen = 0;
+  for (uint64_t c = t0; c < t1; c++) {
+    uint64_t clen = len - c * CRC_UNIT_BYTES;
+    if (clen >= CRC_UNIT_BYTES) {
+      clen = CRC_UNIT_BYTES;
+      crc = t4k[0][crc & 0xFF] ^ t4k[1][(crc >> 8) & 0xFF]
+          ^ t4k[2][(crc >> 16) & 0xFF] ^ t4k[3][crc >> 24];
+    } else {
+      crc = d_crc_shift_lds(mats, crc, clen);
+    }
+    crc ^= unit_crc[u0 + c];
+    mylen += clen;
+  }
+  s_crc[threadIdx.x] = crc;
+  s_len[threadIdx.x] = mylen;
+  __syncthreads();
+  for (int stride = 1; stride < BLOCK; stride <<= 1) {
+    if ((threadIdx.x & (2 * stride - 1)) == 0 && threadIdx.x + stride < BLOCK) {
+      uint64_t rl = s_len[threadIdx.x + stride];
+      if (rl) {
+        s_crc[threadIdx.x] = d_crc_shift_lds(mats, s_crc[threadIdx.x], rl)
+                             ^ s_crc[threadIdx.x + stride];
+        s_len[threadIdx.x] += rl;
       }
     }
-    crc ^= group_crc[g];
+    __syncthreads();
   }
-  if (lane == 0) part_crc[p] = crc;
+  if (threadIdx.x == 0) part_crc[p] = s_crc[0];
 }
 
 /* write headers, EOF trailers and CRC for each partition segment */
@@ -2709,16 +2878,21 @@ static int ensure_device_constants() {
   }
   HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_mats), h_crc_shift_mat, sizeof(h_crc_shift_mat)));
   {
-    /* byte-sliced shift-by-64 / shift-by-256 operators:
+    /* sliced shift-by-64 / -4096 (bytes) and -(256*k), k = 0..15 (nibbles):
      * T[j][b] = (x^(8*N)) * (b << 8j) mod P — so shiftN(crc) is 4 lookups */
-    static uint32_t t64[4][256], t256[4][256];
+    static uint32_t t64[4][256], t4k[4][256], tn[16][8][16];
     for (int j = 0; j < 4; j++)
       for (int b = 0; b < 256; b++) {
         t64[j][b] = gf2_times(h_crc_shift_mat[6], (uint32_t)b << (8 * j));
-        t256[j][b] = gf2_times(h_crc_shift_mat[8], (uint32_t)b << (8 * j));
+        t4k[j][b] = gf2_times(h_crc_shift_mat[12], (uint32_t)b << (8 * j));
       }
+    for (int k = 0; k < 16; k++)
+      for (int j = 0; j < 8; j++)
+        for (int b = 0; b < 16; b++)
+          tn[k][j][b] = h_crc_shift((uint32_t)b << (4 * j), 256ull * k);
     HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_t64), t64, sizeof(t64)));
-    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_t256), t256, sizeof(t256)));
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_t4k), t4k, sizeof(t4k)));
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_tn), tn, sizeof(tn)));
   }
   done = true;
   return 0;
@@ -3718,6 +3892,46 @@ static bool stream_uniform_gate(const RecTable& rt) {
          rt.rec_u0 <= 128 && ((uintptr_t)rt.data0 & 15) == 0;
 }
 
+/* Gate of k_post_sort_meta and the tile skip in k_refine_compact_lb.
+ * TZS_POST_FUSE=0 selects the separate k_eq_init / k_count_nonzero_u8 /
+ * k_part_hist passes and an unskipped compaction; read on every sort, like
+ * TZS_STREAM_UNIFORM. */
+static bool post_fuse_gate() {
+  const char* e = getenv("TZS_POST_FUSE");
+  return !(e && e[0] == '0');
+}
+
+/* CRC32 of P device ranges into d_partcrc[P]: super-chunk layout (the one
+ * place it is computed; WPB unit CRCs per super-chunk), k_crc_chunks,
+ * k_crc_combine_ranges.  d_start/d_len
+ * are the device copies of the range starts and h_len; launches only, no
+ * synchronisation. */
+static int crc_ranges_launch(const uint8_t* d_stream, const uint64_t* d_start,
+                             const uint64_t* d_len, const uint64_t* h_len,
+                             int P, uint32_t* d_partcrc) {
+  static thread_local DBuf d_scbase, d_unitcrc;
+  static thread_local std::vector<uint64_t> h_scbase; /* outlives the upload */
+  if (P <= 0) return 0;
+  h_scbase.assign(P + 1, 0);
+  for (int p = 0; p < P; p++)
+    h_scbase[p + 1] = h_scbase[p] + (h_len[p] + CRC_SC_BYTES - 1) / CRC_SC_BYTES;
+  uint64_t total_sc = h_scbase[P];
+  if (total_sc > 0xFFFFFFFFull) FAIL(-22, "crc: stream too large");
+  if (d_scbase.alloc(8 * (P + 1))) return -12;
+  HIP_CHECK(hipMemcpyAsync(d_scbase.p, h_scbase.data(), 8 * (P + 1),
+                           hipMemcpyHostToDevice));
+  if (d_unitcrc.alloc(4 * WPB * (total_sc ? total_sc : 1))) return -12;
+  if (total_sc)
+    hipLaunchKernelGGL(k_crc_chunks,
+                       dim3((uint32_t)min(total_sc, (uint64_t)4096)), dim3(BLOCK), 0, 0,
+                       d_stream, d_start, d_len, (const uint64_t*)d_scbase.p,
+                       (uint32_t)P, (uint32_t)total_sc, (uint32_t*)d_unitcrc.p);
+  hipLaunchKernelGGL(k_crc_combine_ranges, dim3(P), dim3(BLOCK), 0, 0, d_len,
+                     (const uint64_t*)d_scbase.p, (const uint32_t*)d_unitcrc.p,
+                     d_partcrc);
+  return 0;
+}
+
 /* ---- the core: sort current buffer + emit IFile segments ---- */
 static int sort_and_emit(tzs_sorter* s, HostRT& hrt, uint32_t n,
                          const int32_t* d_part_unsorted,
@@ -3803,7 +4017,21 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
   if (s->eq.alloc(n)) return -12;
   if (s->parts_sorted.alloc(sizeof(uint32_t) * n)) return -12;
   uint8_t* d_eq = (uint8_t*)s->eq.p;
-  if (d_lo)
+  /* fused path: eq, parts, the eq count, the partition starts and the
+     per-tile in-run counts in one pass; one D2H below fetches
+     {neq, pstart[0..P]} */
+  const bool post_fuse = post_fuse_gate();
+  const uint32_t nb_tiles = nblocks_for(n, SCAN_TILE);
+  static thread_local DBuf post_meta, tile_inrun;
+  std::vector<uint32_t> h_meta(P + 2, 0);
+  if (post_fuse) {
+    if (post_meta.alloc(4 * (size_t)(P + 2))) return -12;
+    if (tile_inrun.alloc(4ull * nb_tiles)) return -12;
+    HIP_CHECK(hipMemsetAsync(post_meta.p, 0, 4 * (size_t)(P + 2)));
+    hipLaunchKernelGGL(k_post_sort_meta, dim3(nb_tiles), dim3(BLOCK), 0, 0, d_key,
+                       d_lo, d_eq, pbits, (uint32_t*)s->parts_sorted.p, n, P,
+                       (uint32_t*)post_meta.p, (uint32_t*)tile_inrun.p);
+  } else if (d_lo)
     hipLaunchKernelGGL(k_eq_init2, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_key,
                        d_lo, d_eq, pbits, (uint32_t*)s->parts_sorted.p, n);
   else
@@ -3865,7 +4093,11 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
   /* initial ambiguity count; later levels get it from k_eq_update's
      survivor counter (saves a full-n read per level) */
   uint32_t neq = 0;
-  {
+  if (post_fuse) {
+    HIP_CHECK(hipMemcpy(h_meta.data(), post_meta.p, 4 * (size_t)(P + 2),
+                        hipMemcpyDeviceToHost));
+    neq = h_meta[0];
+  } else {
     HIP_CHECK(hipMemsetAsync(eqcnt.p, 0, 4));
     hipLaunchKernelGGL(k_count_nonzero_u8, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_eq, n,
                        (uint32_t*)eqcnt.p);
@@ -3904,11 +4136,17 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
       if (rc_tick.alloc(32)) return -12;
       HIP_CHECK(hipMemsetAsync(rc_st.p, 0, 8ull * nb_rc));
       HIP_CHECK(hipMemsetAsync(rc_tick.p, 0, 32));
+      /* the skip pays only where tiles can be empty: at most 2*neq
+         positions are in a run, so with neq >= n/16 (Text keys, C3) at
+         least every eighth position may be and the per-block tile_inrun
+         load buys nothing */
+      const bool skip_tiles = post_fuse && (uint64_t)neq * 16 < n;
       hipLaunchKernelGGL(k_refine_compact_lb, dim3(nb_rc), dim3(BLOCK), 0, 0, rt,
                          d_idx, d_eq, n, lb0, use_len, ser_mode, lk0p,
                          (uint64_t*)lkey.p, (uint32_t*)seg.p, (uint32_t*)pos.p,
                          (uint64_t*)rc_st.p, (uint32_t*)rc_tick.p,
-                         (uint32_t*)rc_tick.p + 1, (uint64_t*)rc_tick.p + 2);
+                         (uint32_t*)rc_tick.p + 1, (uint64_t*)rc_tick.p + 2,
+                         skip_tiles ? (const uint32_t*)tile_inrun.p : nullptr);
       uint64_t hh[3] = {0, 0, 0};
       HIP_CHECK(hipMemcpy(hh, rc_tick.p, 24, hipMemcpyDeviceToHost));
       if ((uint32_t)(hh[0] >> 32)) FAIL(-70, "refine compact lookback timeout");
@@ -4186,7 +4424,12 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
   s->skey.release();  /* composites are dead once parts_sorted exists */
   /* partition record ranges: host-side from a partition histogram */
   std::vector<uint32_t> h_pcount(P, 0);
-  {
+  if (post_fuse && !s->combine_applied) {
+    /* sorted order: a partition's count is the distance between two starts */
+    for (int p = 0; p < P; p++) h_pcount[p] = h_meta[2 + p] - h_meta[1 + p];
+  } else {
+    /* the combiner replaced n and parts_sorted: the starts taken before it
+       no longer describe the view */
     static thread_local DBuf d_pc;
     if (d_pc.alloc(sizeof(uint32_t) * P)) return -12;
     HIP_CHECK(hipMemsetAsync(d_pc.p, 0, sizeof(uint32_t) * P));
@@ -4263,7 +4506,7 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
 
   /* upload layout arrays */
   static thread_local DBuf d_segstart, d_body, d_paystart, d_scanbase, d_lastsame,
-      d_present, d_rstart, d_rlen, d_chunkbase, d_partcrc;
+      d_present, d_rstart, d_rlen, d_partcrc;
   auto up = [&](DBuf& b, const void* src, size_t sz) -> int {
     if (b.alloc(sz)) return -12;
     HIP_CHECK(hipMemcpyAsync(b.p, src, sz, hipMemcpyHostToDevice));
@@ -4353,55 +4596,17 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
   }
   (void)hipEventRecord(ev[5]);
 
-  /* 7. CRC: chunk bases per partition */
-  std::vector<uint64_t> h_chunkbase(P + 1, 0);
-  for (int p = 0; p < P; p++)
-    h_chunkbase[p + 1] = h_chunkbase[p] + (h_range_len[p] + CRC_CHUNK - 1) / CRC_CHUNK;
-  uint64_t total_chunks = h_chunkbase[P];
-  if (up(d_chunkbase, h_chunkbase.data(), 8 * (P + 1))) return -12;
-  static thread_local DBuf d_chunkcrc;
-  if (d_chunkcrc.alloc(4 * (total_chunks ? total_chunks : 1))) return -12;
+  /* 7. CRC of every present segment's payload..EOF range */
   if (d_partcrc.alloc(4 * P)) return -12;
   /* patch headers + EOF BEFORE crc (crc covers payload..EOF) */
   hipLaunchKernelGGL(k_patch_segments, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0,
                      d_out, (const uint64_t*)d_segstart.p, (const uint64_t*)d_body.p,
                      (const uint8_t*)d_lastsame.p, (const uint32_t*)d_partcrc.p,
                      (const uint8_t*)d_present.p, P);
-  std::vector<uint64_t> h_scbase(P + 1, 0);
-  for (int p = 0; p < P; p++) {
-    uint64_t nchunks = h_chunkbase[p + 1] - h_chunkbase[p];
-    h_scbase[p + 1] = h_scbase[p] + (nchunks + CRC_SC_CHUNKS - 1) / CRC_SC_CHUNKS;
-  }
-  uint64_t total_sc = h_scbase[P];
-  static thread_local DBuf d_scbase;
-  if (up(d_scbase, h_scbase.data(), 8 * (P + 1))) return -12;
-  if (total_sc)
-    hipLaunchKernelGGL(k_crc_chunks,
-                       dim3((uint32_t)min(total_sc, (uint64_t)4096)), dim3(BLOCK), 0, 0,
-                       d_out, (const uint64_t*)d_rstart.p, (const uint64_t*)d_rlen.p,
-                       (const uint64_t*)d_chunkbase.p, (const uint64_t*)d_scbase.p, P,
-                       (uint32_t)total_sc, (uint32_t*)d_chunkcrc.p);
-  std::vector<uint64_t> h_groupbase(P + 1, 0);
-  for (int p = 0; p < P; p++) {
-    uint64_t nchunks = h_chunkbase[p + 1] - h_chunkbase[p];
-    h_groupbase[p + 1] = h_groupbase[p] + (nchunks + CRC_GROUP_CHUNKS - 1) / CRC_GROUP_CHUNKS;
-  }
-  uint64_t total_groups = h_groupbase[P];
-  static thread_local DBuf d_groupbase, d_groupcrc, d_grouplen;
-  if (up(d_groupbase, h_groupbase.data(), 8 * (P + 1))) return -12;
-  if (d_groupcrc.alloc(4 * (total_groups ? total_groups : 1))) return -12;
-  if (d_grouplen.alloc(8 * (total_groups ? total_groups : 1))) return -12;
-  if (total_groups)
-    hipLaunchKernelGGL(k_crc_combine_groups,
-                       dim3((uint32_t)min(total_groups, (uint64_t)2048)), dim3(BLOCK), 0, 0,
-                       (const uint64_t*)d_rlen.p, (const uint64_t*)d_chunkbase.p,
-                       (const uint64_t*)d_groupbase.p, (const uint32_t*)d_chunkcrc.p, P,
-                       (uint32_t)total_groups, (uint32_t*)d_groupcrc.p,
-                       (uint64_t*)d_grouplen.p);
-  hipLaunchKernelGGL(k_crc_combine_final, dim3((P * WAVE + BLOCK - 1) / BLOCK),
-                     dim3(BLOCK), 0, 0,
-                     (const uint64_t*)d_groupbase.p, (const uint32_t*)d_groupcrc.p,
-                     (const uint64_t*)d_grouplen.p, P, (uint32_t*)d_partcrc.p);
+  rc = crc_ranges_launch(d_out, (const uint64_t*)d_rstart.p,
+                         (const uint64_t*)d_rlen.p, h_range_len.data(), P,
+                         (uint32_t*)d_partcrc.p);
+  if (rc) return rc;
   /* re-patch to write CRC trailers (header/EOF rewrite is idempotent) */
   hipLaunchKernelGGL(k_patch_segments, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0,
                      d_out, (const uint64_t*)d_segstart.p, (const uint64_t*)d_body.p,
@@ -4877,45 +5082,14 @@ static int crc32_ranges(const uint8_t* d_stream,
   int P = (int)starts.size();
   out.assign(P, 0);
   if (P == 0) return 0;
-  std::vector<uint64_t> chunkbase(P + 1, 0), scbase(P + 1, 0), groupbase(P + 1, 0);
-  for (int p = 0; p < P; p++) {
-    uint64_t nchunks = (lens[p] + CRC_CHUNK - 1) / CRC_CHUNK;
-    chunkbase[p + 1] = chunkbase[p] + nchunks;
-    scbase[p + 1] = scbase[p] + (nchunks + CRC_SC_CHUNKS - 1) / CRC_SC_CHUNKS;
-    groupbase[p + 1] = groupbase[p] + (nchunks + CRC_GROUP_CHUNKS - 1) / CRC_GROUP_CHUNKS;
-  }
-  uint64_t total_chunks = chunkbase[P], total_sc = scbase[P], total_groups = groupbase[P];
-  DBuf d_start, d_len, d_cb, d_sb, d_gb, d_cc, d_gc, d_gl, d_pc;
-  auto up2 = [&](DBuf& b, const void* src2, size_t sz) -> int {
-    if (b.alloc(sz)) return -12;
-    HIP_CHECK(hipMemcpyAsync(b.p, src2, sz, hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (up2(d_start, starts.data(), 8 * P)) return -12;
-  if (up2(d_len, lens.data(), 8 * P)) return -12;
-  if (up2(d_cb, chunkbase.data(), 8 * (P + 1))) return -12;
-  if (up2(d_sb, scbase.data(), 8 * (P + 1))) return -12;
-  if (up2(d_gb, groupbase.data(), 8 * (P + 1))) return -12;
-  if (d_cc.alloc(4 * (total_chunks ? total_chunks : 1))) return -12;
-  if (d_gc.alloc(4 * (total_groups ? total_groups : 1))) return -12;
-  if (d_gl.alloc(8 * (total_groups ? total_groups : 1))) return -12;
-  if (d_pc.alloc(4 * P)) return -12;
-  if (total_sc)
-    hipLaunchKernelGGL(k_crc_chunks,
-                       dim3((uint32_t)min(total_sc, (uint64_t)4096)), dim3(BLOCK), 0, 0,
-                       d_stream, (const uint64_t*)d_start.p, (const uint64_t*)d_len.p,
-                       (const uint64_t*)d_cb.p, (const uint64_t*)d_sb.p, P,
-                       (uint32_t)total_sc, (uint32_t*)d_cc.p);
-  if (total_groups)
-    hipLaunchKernelGGL(k_crc_combine_groups,
-                       dim3((uint32_t)min(total_groups, (uint64_t)2048)), dim3(BLOCK), 0, 0,
-                       (const uint64_t*)d_len.p, (const uint64_t*)d_cb.p,
-                       (const uint64_t*)d_gb.p, (const uint32_t*)d_cc.p, P,
-                       (uint32_t)total_groups, (uint32_t*)d_gc.p, (uint64_t*)d_gl.p);
-  hipLaunchKernelGGL(k_crc_combine_final, dim3((P * WAVE + BLOCK - 1) / BLOCK),
-                     dim3(BLOCK), 0, 0, (const uint64_t*)d_gb.p,
-                     (const uint32_t*)d_gc.p, (const uint64_t*)d_gl.p, P,
-                     (uint32_t*)d_pc.p);
+  DBuf d_start, d_len, d_pc;
+  if (d_start.alloc(8 * P) || d_len.alloc(8 * P) || d_pc.alloc(4 * P)) return -12;
+  HIP_CHECK(hipMemcpyAsync(d_start.p, starts.data(), 8 * P, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpyAsync(d_len.p, lens.data(), 8 * P, hipMemcpyHostToDevice));
+  int rc = crc_ranges_launch(d_stream, (const uint64_t*)d_start.p,
+                             (const uint64_t*)d_len.p, lens.data(), P,
+                             (uint32_t*)d_pc.p);
+  if (rc) return rc;
   HIP_CHECK(hipMemcpy(out.data(), d_pc.p, 4 * P, hipMemcpyDeviceToHost));
   return 0;
 }
