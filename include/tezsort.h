@@ -188,7 +188,9 @@ void tzs_sorter_close(tzs_sorter* s);
  * Replaces MergeManager/TezMerger behind OrderedGroupedKVInput
  * (MergeManager.java:423-519,1162-1328; TezMerger.java:466-1066).
  * Segments are device-resident columnar record sets (the xGMI exchange wire,
- * DESIGN.md §4) or IFile-framed bytes.
+ * DESIGN.md §4; tzs_segment, tzs_sorter_add_sorted_segment) or IFile-framed
+ * bytes as a fetcher delivers them (tzs_ifile_decode,
+ * tzs_sorter_add_ifile_segment below).
  */
 typedef struct tzs_segment {
   const void*     d_data;   /* columnar records (key‖val serialized) */
@@ -202,6 +204,42 @@ typedef struct tzs_segment {
  * Emits RLE/SAME_KEY runs per IFile.java:590-615 when rle. */
 int tzs_merge_segments(const tzs_conf* conf, const tzs_segment* segs, int32_t nsegs,
                        void** d_out, int64_t* out_bytes, tzs_index_record* rec);
+
+/* ---- reduce side: IFile-framed segments ----------------------------------
+ * A fetched segment is `TIF\0 | records | EOF | CRC32` (ShuffleHandler
+ * /mapOutput, DISK_DIRECT file.out + index, or a stock mapper).  The device
+ * reader restates IFile.Reader (IFile.java:877-1001: positionToNextRecord,
+ * RLE_MARKER / V_END_MARKER handling, EOF_MARKER) and the trailer check of
+ * IFileInputStream (IFileInputStream.java:84-101).  SAME_KEY records get
+ * their key re-materialised, so the output is plain columnar records.
+ *
+ * Return codes: 0 (or a segment id) on success, 0 records included;
+ * -22 bad arguments, bad magic, header flag other than 0, malformed framing
+ * (tzs_last_error() gives the body offset of the first bad token), missing
+ * EOF marker, segment of 2 GiB or more; -74 CRC mismatch; -12 out of
+ * memory.  Arguments are validated before any device call.  A TIF\1
+ * (compressed) stream is inflated by the caller, who then decodes the
+ * payload with flags = 0. */
+
+/* Decode one IFile stream held in device memory into the columnar form.
+ * flags: bit0 = stream carries the 4-byte header and 4-byte CRC trailer
+ *        bit1 = verify the CRC (needs bit0).
+ * On success d_data, d_off and d_klen receive pool buffers the caller
+ * releases with tzs_free_device (NULLs when *n == 0). */
+int tzs_ifile_decode(const void* d_bytes, int64_t nbytes, int32_t flags,
+                     void** d_data, uint64_t** d_off, uint32_t** d_klen, int64_t* n);
+
+/* Decode + tzs_sorter_add_sorted_segment (MergeManager admission of a fetched
+ * segment, MergeManager.java:423-519).  The sorter owns the decoded
+ * buffers and frees them at close; d_bytes may be released as soon as this
+ * returns.  partition >= 0 stamps every record with that partition id;
+ * -1 recomputes HashPartitioner placement (as d_part == NULL does above).
+ * Also -22 when the segment is not sorted. */
+int tzs_sorter_add_ifile_segment(tzs_sorter* s, const void* d_bytes, int64_t nbytes,
+                                 int32_t flags, int32_t partition);
+
+/* Decoder geometry: out = {chunk bytes, chunks per group}. */
+void tzs_ifile_decode_geometry(uint32_t out[2]);
 
 /* ---- synthetic input generation (bench/tests; device-resident) ---------- */
 /* Seeded deterministic generator of serialized KV records in HBM

@@ -10,5 +10,6 @@ from ._engine import (  # noqa: F401
     Sorter, make_conf, upload_records, generate, free_device, device_available,
     pool_stats,
     merge_segments, read_device,
+    EngineError, upload_bytes, ifile_decode, ifile_decode_geometry,
 )
 from .conf import conf_from_tez_properties  # noqa: F401

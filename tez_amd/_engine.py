@@ -128,6 +128,13 @@ def lib():
     L.tzs_malloc_device.argtypes = [c.c_uint64, c.POINTER(c.c_void_p)]
     L.tzs_pool_stats.argtypes = [c.POINTER(c.c_uint64)]
     L.tzs_pool_stats.restype = None
+    L.tzs_ifile_decode.argtypes = [c.c_void_p, c.c_int64, c.c_int32,
+                                   c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+                                   c.POINTER(c.c_void_p), c.POINTER(c.c_int64)]
+    L.tzs_sorter_add_ifile_segment.argtypes = [c.c_void_p, c.c_void_p, c.c_int64,
+                                               c.c_int32, c.c_int32]
+    L.tzs_ifile_decode_geometry.argtypes = [c.POINTER(c.c_uint32)]
+    L.tzs_ifile_decode_geometry.restype = None
     L.tzs_device_available.restype = c.c_int
     L.tzs_test_crc_combine.restype = c.c_uint32
     L.tzs_test_crc_combine.argtypes = [c.c_uint32, c.c_uint32, c.c_uint64]
@@ -137,10 +144,22 @@ def lib():
     return L
 
 
+class EngineError(RuntimeError):
+    """A negative return code from the native engine; .rc holds the code."""
+
+    def __init__(self, what, rc, msg):
+        super().__init__(f"{what} failed rc={rc}: {msg}")
+        self.rc = rc
+
+
 def _ck(rc, what):
     if rc < 0:
-        raise RuntimeError(f"{what} failed rc={rc}: {lib().tzs_last_error().decode()}")
+        raise EngineError(what, rc, lib().tzs_last_error().decode())
     return rc
+
+
+def _ifile_flags(with_header, verify_crc):
+    return (1 if with_header else 0) | (2 if with_header and verify_crc else 0)
 
 
 def make_conf(num_partitions, **kw):
@@ -184,6 +203,16 @@ class Sorter:
         buffers alive until flush()/close()."""
         return _ck(lib().tzs_sorter_add_sorted_segment(
             self.h, d_data, d_off, d_klen, d_part, n), "add_sorted_segment")
+
+    def add_ifile_segment(self, dev_ptr, nbytes, with_header=True, verify_crc=True,
+                          partition=-1):
+        """Decode an IFile-framed segment held in device memory and ingest it
+        as a sorted segment (no host round trip, no re-sort).  The sorter
+        owns the decoded records; the caller may free dev_ptr on return.
+        partition >= 0 stamps every record; -1 recomputes hash placement."""
+        return _ck(lib().tzs_sorter_add_ifile_segment(
+            self.h, dev_ptr, nbytes, _ifile_flags(with_header, verify_crc),
+            partition), "add_ifile_segment")
 
     def flush(self):
         _ck(lib().tzs_sorter_flush(self.h), "flush")
@@ -378,6 +407,41 @@ def merge_segments(conf, segments):
     if out.value:
         lib().tzs_free_device(out)
     return data, (rec.start_offset, rec.raw_length, rec.part_length)
+
+
+def upload_bytes(data: bytes):
+    """Copy host bytes into a pool buffer (tzs_memcpy_h2d); the caller frees
+    the returned device pointer with free_device."""
+    L = lib()
+    d = ctypes.c_void_p()
+    _ck(L.tzs_malloc_device(max(len(data), 1), ctypes.byref(d)), "malloc")
+    if len(data):
+        _ck(L.tzs_memcpy_h2d(d, bytes(data), len(data)), "h2d")
+    return d
+
+
+def ifile_decode(dev_ptr, nbytes, with_header=True, verify_crc=True):
+    """tzs_ifile_decode: one IFile stream in device memory -> columnar
+    (d_data, d_off, d_klen, n) device pointers (None when n == 0), freed by
+    the caller with free_device.  Raises EngineError (.rc = -22 malformed,
+    -74 CRC mismatch, -12 out of memory)."""
+    d = ctypes.c_void_p()
+    o = ctypes.c_void_p()
+    k = ctypes.c_void_p()
+    n = ctypes.c_int64()
+    _ck(lib().tzs_ifile_decode(dev_ptr, nbytes, _ifile_flags(with_header, verify_crc),
+                               ctypes.byref(d), ctypes.byref(o), ctypes.byref(k),
+                               ctypes.byref(n)), "ifile_decode")
+    if n.value == 0:
+        return None, None, None, 0
+    return d, o, k, n.value
+
+
+def ifile_decode_geometry():
+    """(chunk bytes, chunks per group) of the device IFile decoder."""
+    arr = (ctypes.c_uint32 * 2)()
+    lib().tzs_ifile_decode_geometry(arr)
+    return arr[0], arr[1]
 
 
 def pool_stats():

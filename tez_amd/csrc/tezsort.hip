@@ -2854,6 +2854,409 @@ __global__ void k_fill_fixed_offsets(uint64_t* off, uint32_t* klen_arr, int64_t 
 }
 
 /* ================================================================== */
+/* IFile decode: framed bytes -> columnar records      */
+/* ================================================================== */
+/* The inverse of the emit path (reader contract: IFile.java:877-1001,
+ * restated in tez_amd/ifile.py:read_stream).  Record boundaries form a
+ * sequential chain with one bit of state (inside an RLE run or not), so the
+ * parse is done over NODES: node = 2 * body position + state, state 0 = N
+ * (next token is "klen vlen"), 1 = R (next token is "vlen" or V_END).
+ * next(node) decodes at most three vints; every transition consumes at
+ * least one byte, so orbits strictly advance.  Malformed tokens map to
+ * IFD_BAD, the EOF marker (-1,-1 in state N) to IFD_END, and V_END in state
+ * R folds into the N transition at the following byte.
+ *   k_ifd_chunk_exits : per chunk, next() for all nodes + LDS pointer
+ *                       doubling -> first orbit node outside the chunk
+ *   k_ifd_group_exits : per group of chunks, compose the chunk tables for
+ *                       every entry node of the group's first chunk
+ *   k_ifd_walk        : the one serial step, over groups
+ *   k_ifd_down        : per group, the true entry node of every chunk
+ *   k_ifd_records<0>  : per chunk, count records / bytes on the true orbit
+ *   k_ifd_chunk_scan  : record/byte bases + carried-in key per chunk
+ *   k_ifd_records<1>  : per chunk, write d_off / d_klen / source offsets
+ *   k_ifd_gather      : copy key and value bytes into d_data
+ * Speculative decoding starts at positions that are not record starts, so
+ * every length is range-checked (64-bit sums) before it becomes an index. */
+#define IFD_CHUNK 2048u
+#define IFD_GROUP 64u
+#define IFD_LOOK 32u                   /* staged bytes past the chunk end */
+#define IFD_VPOS (IFD_CHUNK + 24u)     /* positions with a decoded vint */
+#define IFD_END 0xFFFFFFFEu
+#define IFD_BAD 0xFFFFFFFFu
+#define IFD_VBAD (-4)
+#define IFD_MAX_BODY 0x7FFFFFFEull     /* 2 * L + 1 stays below IFD_END */
+
+struct IfdStage {
+  uint32_t by[(IFD_CHUNK + IFD_LOOK) / 4]; /* body bytes, zero past the end */
+  int32_t vval[IFD_VPOS];  /* >= 0 length, -1/-2/-3 markers, IFD_VBAD */
+  uint8_t vsz[IFD_VPOS];   /* encoded size of the vint at this position */
+};
+struct IfdChunkStat {
+  uint64_t bytes_a;   /* record bytes not counting carried-in keys */
+  uint32_t nrec;
+  uint32_t m;         /* SAME_KEY records before the chunk's first key */
+  uint32_t lastk_pos; /* body offset of the chunk's last key, IFD_BAD none */
+  uint32_t lastk_len;
+};
+struct IfdChunkBase {
+  uint64_t byte_base;
+  uint32_t rec_base;
+  uint32_t kpos, klen; /* key carried in from earlier chunks */
+  uint32_t pad;
+};
+struct IfdResult {
+  uint32_t final_node; /* IFD_END on a well-formed stream */
+  uint32_t err_pos;    /* min body offset of a bad token on the true orbit */
+  uint64_t n, total;
+};
+
+/* stage chunk bytes + lookahead and decode the vint at every position */
+__device__ __forceinline__ void d_ifd_stage(IfdStage& S, const uint8_t* body,
+                                            uint32_t L, uint32_t cbase) {
+  const bool al = (((uintptr_t)body) & 3) == 0; /* cbase is a multiple of 4 */
+  uint8_t* by = (uint8_t*)S.by;
+  for (uint32_t w = threadIdx.x; w < (IFD_CHUNK + IFD_LOOK) / 4; w += blockDim.x) {
+    uint64_t g = (uint64_t)cbase + 4ull * w;
+    uint32_t v = 0;
+    if (al && g + 4 <= L) {
+      v = *(const uint32_t*)(body + g);
+    } else {
+      for (int k = 0; k < 4; k++)
+        if (g + k < L) v |= (uint32_t)body[g + k] << (8 * k);
+    }
+    S.by[w] = v;
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < IFD_VPOS; i += blockDim.x) {
+    uint64_t g = (uint64_t)cbase + i;
+    int32_t val = IFD_VBAD;
+    uint32_t sz = 1;
+    if (g < L) {
+      int32_t first = (int8_t)by[i];
+      if (first >= -112) {
+        val = (first >= -3) ? first : IFD_VBAD;
+      } else {
+        bool neg = first < -120;
+        uint32_t nb = (uint32_t)(neg ? -120 - first : -112 - first); /* 1..8 */
+        sz = nb + 1;
+        if (g + sz <= L) {
+          uint64_t mag = 0;
+          for (uint32_t k = 1; k <= nb; k++) mag = (mag << 8) | by[i + k];
+          if (!neg) val = (mag <= 0x7FFFFFFFull) ? (int32_t)mag : IFD_VBAD;
+          else val = (mag <= 2) ? -1 - (int32_t)mag : IFD_VBAD;
+        }
+      }
+    }
+    S.vval[i] = val;
+    S.vsz[i] = (uint8_t)sz;
+  }
+  __syncthreads();
+}
+
+/* transition from state N at local position i (i <= IFD_CHUNK + 8) */
+__device__ __forceinline__ uint32_t d_ifd_next_n(const IfdStage& S, uint32_t i,
+                                                 uint32_t cbase, uint32_t L) {
+  int32_t a = S.vval[i];
+  if (a == IFD_VBAD) return IFD_BAD;
+  uint32_t j = i + S.vsz[i];
+  int32_t b = S.vval[j];
+  if (b == IFD_VBAD) return IFD_BAD;
+  uint64_t p = (uint64_t)cbase + j + S.vsz[j];
+  if (a == -1) return (b == -1) ? IFD_END : IFD_BAD;
+  if (a == -3 || b < 0) return IFD_BAD;
+  uint64_t e = p + (uint64_t)b + (a >= 0 ? (uint64_t)a : 0ull);
+  if (e > L) return IFD_BAD;
+  return (uint32_t)(2 * e) | (a == -2 ? 1u : 0u);
+}
+/* transition from state R at local position i (i < IFD_CHUNK) */
+__device__ __forceinline__ uint32_t d_ifd_next_r(const IfdStage& S, uint32_t i,
+                                                 uint32_t cbase, uint32_t L) {
+  int32_t v = S.vval[i];
+  if (v == -3) return d_ifd_next_n(S, i + S.vsz[i], cbase, L);
+  if (v < 0) return IFD_BAD;
+  uint64_t e = (uint64_t)cbase + i + S.vsz[i] + (uint64_t)v;
+  if (e > L) return IFD_BAD;
+  return (uint32_t)(2 * e) | 1u;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_ifd_chunk_exits(
+    const uint8_t* body, uint32_t L, uint32_t* exitt /* [2 * (L + 1)] */) {
+  __shared__ IfdStage S;
+  __shared__ uint32_t nxt[2 * IFD_CHUNK];
+  const uint32_t cbase = blockIdx.x * IFD_CHUNK;
+  d_ifd_stage(S, body, L, cbase);
+  for (uint32_t i = threadIdx.x; i < IFD_CHUNK; i += blockDim.x) {
+    nxt[2 * i] = d_ifd_next_n(S, i, cbase, L);
+    nxt[2 * i + 1] = d_ifd_next_r(S, i, cbase, L);
+  }
+  __syncthreads();
+  /* pointer doubling, in place: a concurrent update only moves a pointer
+     further along the same orbit, and nodes outside the chunk are fixed
+     points, so any interleaving converges on the chunk exit */
+  for (;;) {
+    int changed = 0;
+    for (uint32_t e = threadIdx.x; e < 2 * IFD_CHUNK; e += blockDim.x) {
+      uint32_t v = nxt[e];
+      if (v < IFD_END && (v >> 1) - cbase < IFD_CHUNK) {
+        nxt[e] = nxt[v - 2 * cbase];
+        changed = 1;
+      }
+    }
+    if (!__syncthreads_or(changed)) break;
+  }
+  for (uint32_t e = threadIdx.x; e < 2 * IFD_CHUNK; e += blockDim.x)
+    if ((uint64_t)cbase + (e >> 1) <= L) exitt[2ull * cbase + e] = nxt[e];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_ifd_group_exits(
+    const uint32_t* exitt, uint32_t L, uint32_t* gexit /* [ngroups][2 * CHUNK] */) {
+  const uint32_t gbase = blockIdx.x * (IFD_GROUP * IFD_CHUNK);
+  const uint32_t gend = gbase + IFD_GROUP * IFD_CHUNK;
+  for (uint32_t e = threadIdx.x; e < 2 * IFD_CHUNK; e += blockDim.x) {
+    uint32_t node = IFD_BAD;
+    if ((uint64_t)gbase + (e >> 1) <= L) {
+      node = 2 * gbase + e;
+      do node = exitt[node]; while (node < IFD_END && (node >> 1) < gend);
+    }
+    gexit[(uint64_t)blockIdx.x * (2 * IFD_CHUNK) + e] = node;
+  }
+}
+
+__global__ void k_ifd_walk(const uint32_t* exitt, const uint32_t* gexit,
+                           uint32_t* gentry, IfdResult* res) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t node = 0;
+  while (node < IFD_END) {
+    uint32_t pos = node >> 1;
+    uint32_t g = pos / (IFD_GROUP * IFD_CHUNK);
+    uint32_t gbase = g * (IFD_GROUP * IFD_CHUNK);
+    uint32_t gend = gbase + IFD_GROUP * IFD_CHUNK;
+    gentry[g] = node;
+    if (pos - gbase < IFD_CHUNK) {
+      node = gexit[(uint64_t)g * (2 * IFD_CHUNK) + (node - 2 * gbase)];
+    } else {
+      do node = exitt[node]; while (node < IFD_END && (node >> 1) < gend);
+    }
+  }
+  res->final_node = node;
+}
+
+__global__ void k_ifd_down(const uint32_t* exitt, const uint32_t* gentry,
+                           uint32_t ngroups, uint32_t* centry) {
+  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ngroups) return;
+  uint32_t node = gentry[g];
+  uint32_t gend = (g + 1) * (IFD_GROUP * IFD_CHUNK);
+  while (node < IFD_END && (node >> 1) < gend) {
+    centry[(node >> 1) / IFD_CHUNK] = node;
+    node = exitt[node];
+  }
+}
+
+/* Walk the true orbit inside one chunk (LDS only).  WRITE = false counts;
+ * WRITE = true writes the record table. */
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK) void k_ifd_records(
+    const uint8_t* body, uint32_t L, const uint32_t* centry,
+    IfdChunkStat* cst, const IfdChunkBase* cbs, IfdResult* res,
+    uint64_t* d_off, uint32_t* d_klen, uint2* src /* {key pos, value pos} */) {
+  __shared__ IfdStage S;
+  const uint32_t c = blockIdx.x;
+  const uint32_t cbase = c * IFD_CHUNK;
+  const uint32_t entry = centry[c];
+  if (entry >= IFD_END) { /* the orbit jumps over this chunk */
+    if (!WRITE && threadIdx.x == 0) {
+      IfdChunkStat z = {0, 0, 0, IFD_BAD, 0};
+      cst[c] = z;
+    }
+    return;
+  }
+  d_ifd_stage(S, body, L, cbase);
+  if (threadIdx.x != 0) return;
+  uint32_t node = entry;
+  uint32_t nrec = 0, m = 0, kpos = IFD_BAD, klen = 0;
+  uint64_t bytes = 0, r = 0;
+  bool havekey = false;
+  if (WRITE) {
+    IfdChunkBase b = cbs[c];
+    r = b.rec_base; bytes = b.byte_base; kpos = b.kpos; klen = b.klen;
+  }
+  while (node < IFD_END && (node >> 1) - cbase < IFD_CHUNK) {
+    uint32_t i = (node >> 1) - cbase;
+    uint32_t st = node & 1;
+    uint32_t nx = st ? d_ifd_next_r(S, i, cbase, L) : d_ifd_next_n(S, i, cbase, L);
+    if (nx == IFD_BAD) {
+      if (!WRITE) atomicMin(&res->err_pos, node >> 1);
+      break;
+    }
+    if (nx == IFD_END) break;
+    /* nx is valid, so every offset below was range-checked by next() */
+    if (st && S.vval[i] == -3) { i += S.vsz[i]; st = 0; }
+    uint32_t vlen, vpos;
+    bool same = true;
+    if (st) {
+      vlen = (uint32_t)S.vval[i];
+      vpos = cbase + i + S.vsz[i];
+    } else {
+      int32_t a = S.vval[i];
+      uint32_t j = i + S.vsz[i];
+      vlen = (uint32_t)S.vval[j];
+      vpos = cbase + j + S.vsz[j];
+      if (a >= 0) {
+        same = false; havekey = true;
+        kpos = vpos; klen = (uint32_t)a; vpos += klen;
+      }
+    }
+    if (WRITE) {
+      d_off[r] = bytes;
+      d_klen[r] = klen;
+      src[r] = make_uint2(kpos == IFD_BAD ? 0u : kpos, vpos);
+      r++;
+      bytes += (uint64_t)klen + vlen;
+    } else {
+      nrec++;
+      if (same && !havekey) { m++; bytes += vlen; }
+      else bytes += (uint64_t)klen + vlen;
+    }
+    node = nx;
+  }
+  if (!WRITE) {
+    IfdChunkStat o = {bytes, nrec, m, havekey ? kpos : IFD_BAD, havekey ? klen : 0u};
+    cst[c] = o;
+  }
+}
+
+/* block scan (sum, or max when MAXOP): wave shuffles plus one LDS hop for
+ * the wave totals.  Returns the inclusive value; *excl the exclusive one and
+ * *total the block total. */
+#define IFD_SCAN_BLOCK 1024
+template <bool MAXOP>
+__device__ __forceinline__ uint64_t d_ifd_block_scan(uint64_t v, uint64_t* wtot,
+                                                     uint64_t* excl, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = threadIdx.x / WAVE;
+  uint64_t inc = v;
+  for (int s = 1; s < WAVE; s <<= 1) {
+    uint64_t u = __shfl_up((unsigned long long)inc, s);
+    if (lane >= (uint32_t)s) inc = MAXOP ? (u > inc ? u : inc) : inc + u;
+  }
+  uint64_t prev = __shfl_up((unsigned long long)inc, 1);
+  if (lane == 0) prev = 0;
+  __syncthreads(); /* the previous scan's wtot readers are done */
+  if (lane == WAVE - 1) wtot[wv] = inc;
+  __syncthreads();
+  uint64_t pre = 0, tot = 0;
+  for (uint32_t w = 0; w < IFD_SCAN_BLOCK / WAVE; w++) {
+    uint64_t x = wtot[w];
+    if (w == wv) pre = tot;
+    tot = MAXOP ? (x > tot ? x : tot) : tot + x;
+  }
+  *excl = MAXOP ? (pre > prev ? pre : prev) : pre + prev;
+  *total = tot;
+  return MAXOP ? (pre > inc ? pre : inc) : pre + inc;
+}
+
+/* One block: per chunk the exclusive record / byte bases and the key carried
+ * in from the nearest earlier chunk that holds one (running max of chunk
+ * ids), tile after tile with carries. */
+__global__ __launch_bounds__(IFD_SCAN_BLOCK) void k_ifd_chunk_scan(
+    const IfdChunkStat* cst, uint32_t nchunks, IfdChunkBase* cbs, IfdResult* res) {
+  __shared__ uint64_t wtot[IFD_SCAN_BLOCK / WAVE];
+  const uint32_t t = threadIdx.x;
+  uint64_t carry_rec = 0, carry_bytes = 0, carry_key = 0; /* key: chunk id + 1 */
+  for (uint32_t base = 0; base < nchunks; base += IFD_SCAN_BLOCK) {
+    uint32_t c = base + t;
+    IfdChunkStat st = {0, 0, 0, IFD_BAD, 0};
+    if (c < nchunks) st = cst[c];
+    uint64_t kx, ktot, eb, tot_b, er, tot_r;
+    d_ifd_block_scan<true>(st.lastk_pos != IFD_BAD ? (uint64_t)c + 1 : 0ull, wtot,
+                           &kx, &ktot);
+    if (carry_key > kx) kx = carry_key;
+    uint32_t kpos = IFD_BAD, klen = 0;
+    if (kx) { kpos = cst[kx - 1].lastk_pos; klen = cst[kx - 1].lastk_len; }
+    uint64_t bytes = st.bytes_a + (uint64_t)st.m * klen;
+    d_ifd_block_scan<false>(bytes, wtot, &eb, &tot_b);
+    d_ifd_block_scan<false>(st.nrec, wtot, &er, &tot_r);
+    if (c < nchunks) {
+      IfdChunkBase o;
+      o.byte_base = carry_bytes + eb;
+      o.rec_base = (uint32_t)(carry_rec + er);
+      o.kpos = kpos; o.klen = klen; o.pad = 0;
+      cbs[c] = o;
+    }
+    carry_bytes += tot_b;
+    carry_rec += tot_r;
+    if (ktot > carry_key) carry_key = ktot;
+  }
+  if (t == 0) { res->n = carry_rec; res->total = carry_bytes; }
+}
+
+/* wave-cooperative copy.  Long runs go as 16-byte stores to an aligned
+ * destination, the source read as aligned words and funnel-shifted; vectors
+ * whose covering words are not wholly inside [lo, hi) fall back to bytes. */
+__device__ __forceinline__ void d_ifd_wave_copy(uint8_t* dst, const uint8_t* src,
+                                                uint32_t len, uint32_t lane,
+                                                const uint8_t* lo, const uint8_t* hi) {
+  if (len < 96) {
+    for (uint32_t b = lane; b < len; b += WAVE) dst[b] = src[b];
+    return;
+  }
+  uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
+  if (lane < head) dst[lane] = src[lane];
+  dst += head; src += head; len -= head;
+  const uint32_t nv = len >> 4;
+  const uint32_t sh = (uint32_t)((uintptr_t)src & 3);
+  for (uint32_t v = lane; v < nv; v += WAVE) {
+    const uint8_t* s = src + 16ull * v;
+    const uint8_t* a = s - sh;
+    if (a >= lo && a + (sh ? 20 : 16) <= hi) {
+      const uint32_t* w = (const uint32_t*)a;
+      uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+      uint4 o;
+      if (sh) {
+        uint32_t w4 = w[4];
+        uint32_t r = 8 * sh;
+        o.x = (uint32_t)((((uint64_t)w1 << 32) | w0) >> r);
+        o.y = (uint32_t)((((uint64_t)w2 << 32) | w1) >> r);
+        o.z = (uint32_t)((((uint64_t)w3 << 32) | w2) >> r);
+        o.w = (uint32_t)((((uint64_t)w4 << 32) | w3) >> r);
+      } else {
+        o = make_uint4(w0, w1, w2, w3);
+      }
+      *(uint4*)(dst + 16ull * v) = o;
+    } else {
+      for (int k = 0; k < 16; k++) dst[16ull * v + k] = s[k];
+    }
+  }
+  uint32_t tail = len & 15;
+  if (lane < tail) dst[16ull * nv + lane] = src[16ull * nv + lane];
+}
+
+/* one wave per record: key ‖ value into d_data (the mirror of k_emit_records).
+ * A record that carries its own key is one contiguous source run. */
+__global__ __launch_bounds__(BLOCK) void k_ifd_gather(
+    const uint8_t* body, const uint8_t* lo, const uint8_t* hi,
+    const uint64_t* d_off, const uint32_t* d_klen, const uint2* src,
+    uint8_t* d_data, uint32_t n) {
+  uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  uint32_t nwaves = (gridDim.x * blockDim.x) / WAVE;
+  for (uint32_t i = wave; i < n; i += nwaves) {
+    uint64_t o = d_off[i];
+    uint32_t len = (uint32_t)(d_off[i + 1] - o);
+    uint32_t klen = d_klen[i];
+    uint2 sp = src[i];
+    uint8_t* w = d_data + o;
+    if (sp.y == sp.x + klen) {
+      d_ifd_wave_copy(w, body + sp.x, len, lane, lo, hi);
+    } else {
+      d_ifd_wave_copy(w, body + sp.x, klen, lane, lo, hi);
+      d_ifd_wave_copy(w + klen, body + sp.y, len - klen, lane, lo, hi);
+    }
+  }
+}
+
+/* ================================================================== */
 /* host-side engine                                                    */
 /* ================================================================== */
 namespace {
@@ -5560,6 +5963,200 @@ extern "C" int tzs_merge_segments(const tzs_conf* conf, const tzs_segment* segs,
   if (rec) *rec = ix;
   tzs_sorter_close(s);
   return 0;
+}
+
+/* ---- reduce-side IFile segment decode ----------------------------------
+ * Fetched segments arrive IFile-framed (ShuffleHandler /mapOutput, local
+ * file.out + index, stock mappers): IFile.java:877-1001 positionToNextRecord
+ * and IFileInputStream.java:84-101 (CRC trailer) restated on the device.
+ * Kernel pipeline: see the k_ifd_* block.  Scratch is pool memory released
+ * on return: 8 bytes per body byte (the chunk exit table) + 8 bytes per
+ * record. */
+static int ifile_decode_check_args(const void* d_bytes, int64_t nbytes, int32_t flags) {
+  if (nbytes < 0) FAIL(-22, "ifile_decode: negative nbytes");
+  if (flags & ~3) FAIL(-22, "ifile_decode: unknown flags 0x%x", flags);
+  if ((flags & 2) && !(flags & 1))
+    FAIL(-22, "ifile_decode: CRC verification needs the header/trailer flag");
+  if (nbytes >= (1ll << 31))
+    FAIL(-22, "ifile_decode: segment too large (%lld bytes, limit 2 GiB)",
+         (long long)nbytes);
+  if ((flags & 1) && nbytes < 8)
+    FAIL(-22, "ifile_decode: truncated stream (%lld bytes hold no header and trailer)",
+         (long long)nbytes);
+  if (!(flags & 1) && nbytes == 0)
+    FAIL(-22, "ifile_decode: malformed framing at body offset 0 (no EOF marker)");
+  if (!d_bytes) FAIL(-22, "ifile_decode: null stream");
+  return 0;
+}
+
+static int ifile_decode_impl(const void* d_bytes, int64_t nbytes, int32_t flags,
+                             DBuf& o_data, DBuf& o_off, DBuf& o_klen,
+                             int64_t* o_n, uint64_t* o_total) {
+  if (ensure_device_constants()) return -70;
+  const uint8_t* base = (const uint8_t*)d_bytes;
+  const uint8_t* body = base;
+  uint64_t L = (uint64_t)nbytes;
+  if (flags & 1) {
+    uint8_t hdr[4], trl[4];
+    HIP_CHECK(hipMemcpy(hdr, base, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(trl, base + nbytes - 4, 4, hipMemcpyDeviceToHost));
+    if (memcmp(hdr, "TIF", 3) != 0) FAIL(-22, "ifile_decode: bad IFile magic");
+    body = base + 4;
+    L = (uint64_t)nbytes - 8;
+    if (flags & 2) {
+      /* the checksum sits below the codec: it covers the payload as stored
+         (IFileInputStream.java:84-101), whatever the header flag says */
+      DBuf crcb;
+      if (crcb.alloc(32)) return -12;
+      uint64_t mis = (uint64_t)((uintptr_t)base & 3); /* CRC words are 4-aligned */
+      uint64_t h[3] = {4 + mis, L, 0};
+      HIP_CHECK(hipMemcpy(crcb.p, h, 24, hipMemcpyHostToDevice));
+      int rc = crc_ranges_launch(base - mis, (const uint64_t*)crcb.p,
+                                 (const uint64_t*)crcb.p + 1, &L, 1,
+                                 (uint32_t*)((uint64_t*)crcb.p + 2));
+      if (rc) return rc;
+      uint32_t got = 0;
+      HIP_CHECK(hipMemcpy(&got, (uint64_t*)crcb.p + 2, 4, hipMemcpyDeviceToHost));
+      uint32_t want = ((uint32_t)trl[0] << 24) | ((uint32_t)trl[1] << 16) |
+                      ((uint32_t)trl[2] << 8) | trl[3];
+      if (got != want)
+        FAIL(-74, "ifile_decode: IFile CRC mismatch (computed %08x, trailer %08x)",
+             got, want);
+    }
+    if (hdr[3] == 1)
+      FAIL(-22, "ifile_decode: compressed (TIF\\1) payload; inflate it on the "
+                "host and decode the payload without the header flag");
+    if (hdr[3] != 0)
+      FAIL(-22, "ifile_decode: unknown IFile compression flag %u", hdr[3]);
+  }
+  if (L > IFD_MAX_BODY) FAIL(-22, "ifile_decode: segment too large");
+  const uint32_t L32 = (uint32_t)L;
+  const uint32_t nchunks = L32 / IFD_CHUNK + 1; /* the node at L has a slot */
+  const uint32_t ngroups = L32 / (IFD_GROUP * IFD_CHUNK) + 1;
+  DBuf exitt, gexit, gentry, centry, cst, cbs, resb, srcb;
+  if (exitt.alloc(8ull * (L + 1))) return -12;
+  if (gexit.alloc(8ull * IFD_CHUNK * ngroups)) return -12;
+  if (gentry.alloc(4ull * ngroups)) return -12;
+  if (centry.alloc(4ull * nchunks)) return -12;
+  if (cst.alloc(sizeof(IfdChunkStat) * (uint64_t)nchunks)) return -12;
+  if (cbs.alloc(sizeof(IfdChunkBase) * (uint64_t)nchunks)) return -12;
+  if (resb.alloc(sizeof(IfdResult))) return -12;
+  IfdResult hres = {IFD_BAD, IFD_BAD, 0, 0};
+  HIP_CHECK(hipMemcpy(resb.p, &hres, sizeof(hres), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemsetAsync(gentry.p, 0xFF, 4ull * ngroups));
+  HIP_CHECK(hipMemsetAsync(centry.p, 0xFF, 4ull * nchunks));
+  hipLaunchKernelGGL(k_ifd_chunk_exits, dim3(nchunks), dim3(BLOCK), 0, 0, body, L32,
+                     (uint32_t*)exitt.p);
+  hipLaunchKernelGGL(k_ifd_group_exits, dim3(ngroups), dim3(BLOCK), 0, 0,
+                     (const uint32_t*)exitt.p, L32, (uint32_t*)gexit.p);
+  hipLaunchKernelGGL(k_ifd_walk, dim3(1), dim3(WAVE), 0, 0, (const uint32_t*)exitt.p,
+                     (const uint32_t*)gexit.p, (uint32_t*)gentry.p,
+                     (IfdResult*)resb.p);
+  hipLaunchKernelGGL(k_ifd_down, dim3(nblocks_for(ngroups, BLOCK)), dim3(BLOCK), 0, 0,
+                     (const uint32_t*)exitt.p, (const uint32_t*)gentry.p, ngroups,
+                     (uint32_t*)centry.p);
+  hipLaunchKernelGGL(k_ifd_records<false>, dim3(nchunks), dim3(BLOCK), 0, 0, body, L32,
+                     (const uint32_t*)centry.p, (IfdChunkStat*)cst.p,
+                     (const IfdChunkBase*)nullptr, (IfdResult*)resb.p,
+                     (uint64_t*)nullptr, (uint32_t*)nullptr, (uint2*)nullptr);
+  hipLaunchKernelGGL(k_ifd_chunk_scan, dim3(1), dim3(IFD_SCAN_BLOCK), 0, 0,
+                     (const IfdChunkStat*)cst.p, nchunks, (IfdChunkBase*)cbs.p,
+                     (IfdResult*)resb.p);
+  HIP_CHECK(hipMemcpy(&hres, resb.p, sizeof(hres), hipMemcpyDeviceToHost));
+  if (hres.final_node != IFD_END) {
+    if (hres.err_pos >= L)
+      FAIL(-22, "ifile_decode: malformed framing at body offset %llu "
+                "(stream ends without an EOF marker)", (unsigned long long)L);
+    FAIL(-22, "ifile_decode: malformed framing at body offset %u "
+              "(bad length token or record past the end)", hres.err_pos);
+  }
+  *o_n = (int64_t)hres.n;
+  *o_total = hres.total;
+  if (hres.n == 0) return 0;
+  const uint32_t n = (uint32_t)hres.n;
+  if (o_off.alloc(8ull * (n + 1ull))) return -12;
+  if (o_klen.alloc(4ull * n)) return -12;
+  if (o_data.alloc(hres.total ? hres.total : 1)) return -12;
+  if (srcb.alloc(8ull * n)) return -12;
+  HIP_CHECK(hipMemcpy((uint64_t*)o_off.p + n, &hres.total, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_ifd_records<true>, dim3(nchunks), dim3(BLOCK), 0, 0, body, L32,
+                     (const uint32_t*)centry.p, (IfdChunkStat*)nullptr,
+                     (const IfdChunkBase*)cbs.p, (IfdResult*)resb.p,
+                     (uint64_t*)o_off.p, (uint32_t*)o_klen.p, (uint2*)srcb.p);
+  const uint8_t* lo = (const uint8_t*)(((uintptr_t)base + 3) & ~(uintptr_t)3);
+  const uint8_t* hi = (const uint8_t*)(((uintptr_t)base + (uint64_t)nbytes) & ~(uintptr_t)3);
+  hipLaunchKernelGGL(k_ifd_gather, dim3(grid_waves(n)), dim3(BLOCK), 0, 0, body, lo, hi,
+                     (const uint64_t*)o_off.p, (const uint32_t*)o_klen.p,
+                     (const uint2*)srcb.p, (uint8_t*)o_data.p, n);
+  HIP_CHECK(hipDeviceSynchronize());
+  return 0;
+}
+
+/* hand a DBuf's buffer to the caller as a tzs_free_device-able allocation */
+static void* dbuf_export(DBuf& b) {
+  void* p = b.p;
+  if (p) {
+    std::lock_guard<std::mutex> lk(pool_mu());
+    pool_registry()[p] = b.sz;
+  }
+  b.p = nullptr;
+  b.sz = 0;
+  return p;
+}
+
+extern "C" void tzs_ifile_decode_geometry(uint32_t out[2]) {
+  out[0] = IFD_CHUNK;
+  out[1] = IFD_GROUP;
+}
+
+extern "C" int tzs_ifile_decode(const void* d_bytes, int64_t nbytes, int32_t flags,
+                                void** d_data, uint64_t** d_off, uint32_t** d_klen,
+                                int64_t* n) {
+  int rc = ifile_decode_check_args(d_bytes, nbytes, flags);
+  if (rc) return rc;
+  if (!d_data || !d_off || !d_klen || !n) FAIL(-22, "ifile_decode: null output");
+  *d_data = nullptr; *d_off = nullptr; *d_klen = nullptr; *n = 0;
+  DBuf data, off, klen;
+  uint64_t total = 0;
+  rc = ifile_decode_impl(d_bytes, nbytes, flags, data, off, klen, n, &total);
+  if (rc) return rc;
+  if (*n == 0) return 0;
+  *d_data = dbuf_export(data);
+  *d_off = (uint64_t*)dbuf_export(off);
+  *d_klen = (uint32_t*)dbuf_export(klen);
+  return 0;
+}
+
+extern "C" int tzs_sorter_add_ifile_segment(tzs_sorter* s, const void* d_bytes,
+                                            int64_t nbytes, int32_t flags,
+                                            int32_t partition) {
+  if (!s) FAIL(-22, "add_ifile_segment: null sorter");
+  int rc = ifile_decode_check_args(d_bytes, nbytes, flags);
+  if (rc) return rc;
+  if (partition < -1 || partition >= s->conf.num_partitions)
+    FAIL(-22, "add_ifile_segment: partition %d out of range", partition);
+  if (s->cur_n != 0 || !s->host_klen.empty())
+    FAIL(-22, "add_ifile_segment cannot mix with buffered writes");
+  DBuf data, off, klen, part;
+  int64_t n = 0;
+  uint64_t total = 0;
+  rc = ifile_decode_impl(d_bytes, nbytes, flags, data, off, klen, &n, &total);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (partition >= 0) {
+    if (part.alloc(4ull * n)) return -12;
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)part.p, partition, (size_t)n));
+  }
+  rc = tzs_sorter_add_sorted_segment(s, data.p, (const uint64_t*)off.p,
+                                     (const uint32_t*)klen.p,
+                                     (const int32_t*)part.p, n);
+  if (rc < 0) return rc;
+  /* the sorter owns the decoded buffers from here (released at close) */
+  SpillData* sp = s->spills[rc];
+  sp->data = std::move(data);
+  sp->off = std::move(off);
+  sp->klen = std::move(klen);
+  return rc;
 }
 
 /* ---- misc helpers for the Python layer ---- */

@@ -3,8 +3,9 @@
 Restates the reader semantics of IFile.Reader
 (IFile.java:877-1001: positionToNextRecord / RLE & V_END handling) and the
 vint codec (hadoop WritableUtils).  Pure Python — used by the plugin input
-to ingest fetched segments; the hot path (sort/merge/emit) never goes
-through here.
+to walk the merged output for its reader, and the semantic contract of the
+device reader (tzs_ifile_decode); the hot path (decode/sort/merge/emit)
+never goes through here.
 """
 import zlib
 
