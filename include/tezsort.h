@@ -241,6 +241,57 @@ int tzs_sorter_add_ifile_segment(tzs_sorter* s, const void* d_bytes, int64_t nby
 /* Decoder geometry: out = {chunk bytes, chunks per group}. */
 void tzs_ifile_decode_geometry(uint32_t out[2]);
 
+/* ---- reduce side: grouped key/values view --------------------------------
+ * KeyValuesReader.next() / getCurrentKey() / getCurrentValues() with the
+ * grouping of ValuesIterator.java:177-199, delivered as CSR arrays in device
+ * memory: group g owns records d_group_off[g] .. d_group_off[g+1] of the
+ * sorted record set, its serialized key is d_key_data[d_key_off[g] ..
+ * d_key_off[g+1]], and record i's serialized value is
+ * d_val_data[d_val_off[i] .. d_val_off[i+1]].
+ *
+ * Group rule: record i starts a group iff it is the first record of the
+ * partition or its serialized key differs from record i-1's (equal length
+ * and equal bytes is what both comparators call equal; under TZS_CMP_TEXT
+ * "ab" and "abc" are two groups).  RLE framing and spill provenance play no
+ * part.
+ *
+ * Return codes: 0 on success; -22 (before any device call) for a null
+ * sorter, a null out, a partition outside [0, num_partitions), a sorter that
+ * is not flushed, a sorter whose final merge is disabled and that holds more
+ * than one spill (there is no merged set), a negative n or null columns with
+ * n > 0; -12 out of memory, everything allocated so far released.  The
+ * output buffers are pool buffers owned by the caller, who releases them
+ * with the free call below; all are NULL when n_records == 0. */
+typedef struct tzs_groups {
+  int64_t   n_records, n_groups;
+  uint64_t* d_group_off;  /* [n_groups+1] first record of each group; last = n_records */
+  void*     d_key_data;   /* one SERIALIZED key per group, contiguous */
+  uint64_t* d_key_off;    /* [n_groups+1] */
+  void*     d_val_data;   /* serialized values of all records, sorted order, contiguous */
+  uint64_t* d_val_off;    /* [n_records+1] */
+} tzs_groups;
+
+/* Groups of partition `partition` of the final merged record set.  Valid
+ * after flush(): after one spill, after the k-way merge of several, after
+ * sorted-segment or IFile-segment admission, and with the combiner applied
+ * (one value per group then).  Reads the merged records in place; neither
+ * the IFile stream nor a columnar copy is involved. */
+int tzs_sorter_grouped(tzs_sorter* s, int32_t partition, tzs_groups* out);
+
+/* The same grouping over a caller's columnar segment of one partition
+ * (conf gives the key type).  Groups are runs of ADJACENT equal keys: the
+ * segment is NOT checked for sortedness, and a key that recurs after a
+ * different one starts another group. */
+int tzs_group_sorted(const tzs_conf* conf, const tzs_segment* seg, tzs_groups* out);
+
+/* Release the buffers of a grouped view and null its pointers.  A null
+ * struct or null members are a no-op. */
+void tzs_groups_free(tzs_groups* g);
+
+/* Grouping geometry: out = {positions per block tile of the flags pass,
+ * key length from which a wide compare applies, or 0 when there is none}. */
+void tzs_group_geometry(uint32_t out[2]);
+
 /* ---- synthetic input generation (bench/tests; device-resident) ---------- */
 /* Seeded deterministic generator of serialized KV records in HBM
  * (shapes of BASELINE.json configs). kind: 0 = C2 (fixed klen random unique

@@ -11,5 +11,6 @@ from ._engine import (  # noqa: F401
     pool_stats,
     merge_segments, read_device,
     EngineError, upload_bytes, ifile_decode, ifile_decode_geometry,
+    Groups, group_sorted, group_geometry,
 )
 from .conf import conf_from_tez_properties  # noqa: F401

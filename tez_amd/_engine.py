@@ -47,6 +47,13 @@ class TzsSegment(ctypes.Structure):
                 ("d_klen", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
+class TzsGroups(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_int64), ("n_groups", ctypes.c_int64),
+                ("d_group_off", ctypes.c_void_p), ("d_key_data", ctypes.c_void_p),
+                ("d_key_off", ctypes.c_void_p), ("d_val_data", ctypes.c_void_p),
+                ("d_val_off", ctypes.c_void_p)]
+
+
 class TzsCounters(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in
                 ("output_records", "output_bytes", "output_bytes_with_overhead",
@@ -135,6 +142,13 @@ def lib():
                                                c.c_int32, c.c_int32]
     L.tzs_ifile_decode_geometry.argtypes = [c.POINTER(c.c_uint32)]
     L.tzs_ifile_decode_geometry.restype = None
+    L.tzs_sorter_grouped.argtypes = [c.c_void_p, c.c_int32, c.POINTER(TzsGroups)]
+    L.tzs_group_sorted.argtypes = [c.POINTER(TzsConf), c.POINTER(TzsSegment),
+                                   c.POINTER(TzsGroups)]
+    L.tzs_groups_free.argtypes = [c.POINTER(TzsGroups)]
+    L.tzs_groups_free.restype = None
+    L.tzs_group_geometry.argtypes = [c.POINTER(c.c_uint32)]
+    L.tzs_group_geometry.restype = None
     L.tzs_device_available.restype = c.c_int
     L.tzs_test_crc_combine.restype = c.c_uint32
     L.tzs_test_crc_combine.argtypes = [c.c_uint32, c.c_uint32, c.c_uint64]
@@ -283,6 +297,13 @@ class Sorter:
                                              ctypes.byref(k), rr, br),
             "sorted_columnar")
         return d, o, k, list(rr), list(br)
+
+    def grouped(self, partition):
+        """Key groups of one partition of the merged record set as device
+        CSR arrays (tzs_sorter_grouped); returns a Groups object."""
+        g = TzsGroups()
+        _ck(lib().tzs_sorter_grouped(self.h, partition, ctypes.byref(g)), "grouped")
+        return Groups(g)
 
     def write_files_compressed(self, local_dir: str, unique_id: str):
         """Reference on-disk layout with DefaultCodec segments: the TIF\\1
@@ -441,6 +462,77 @@ def ifile_decode_geometry():
     """(chunk bytes, chunks per group) of the device IFile decoder."""
     arr = (ctypes.c_uint32 * 2)()
     lib().tzs_ifile_decode_geometry(arr)
+    return arr[0], arr[1]
+
+
+class Groups:
+    """Device-resident grouped view (tzs_groups): .n_records, .n_groups and
+    the five device pointers in .g.  free() returns the buffers to the pool;
+    it is idempotent and also runs from __del__."""
+
+    def __init__(self, g: TzsGroups):
+        self.g = g
+        self.n_records = g.n_records
+        self.n_groups = g.n_groups
+
+    def to_host(self):
+        """(key_data u8, key_off u64, val_data u8, val_off u64, group_off u64)
+        as numpy arrays; the offset arrays are [0] when there are no records."""
+        import numpy as np
+        g = self.g
+        n, ng = self.n_records, self.n_groups
+        if n == 0:
+            z = np.zeros(1, dtype=np.uint64)
+            e = np.zeros(0, dtype=np.uint8)
+            return e, z.copy(), e.copy(), z.copy(), z.copy()
+        if not g.d_val_off:
+            raise RuntimeError("grouped view already freed")
+
+        def pull(ptr, count, dtype):
+            a = np.empty(count, dtype=dtype)
+            if a.nbytes:
+                _ck(lib().tzs_memcpy_d2h(a.ctypes.data, ptr, a.nbytes), "d2h")
+            return a
+
+        key_off = pull(g.d_key_off, ng + 1, np.uint64)
+        val_off = pull(g.d_val_off, n + 1, np.uint64)
+        group_off = pull(g.d_group_off, ng + 1, np.uint64)
+        key_data = pull(g.d_key_data, int(key_off[-1]), np.uint8)
+        val_data = pull(g.d_val_data, int(val_off[-1]), np.uint8)
+        return key_data, key_off, val_data, val_off, group_off
+
+    def free(self):
+        if self.g is not None and _lib is not None:
+            _lib.tzs_groups_free(ctypes.byref(self.g))
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def group_sorted(conf, segment):
+    """tzs_group_sorted: segment = (d_data, d_off, d_klen, n) device pointers
+    of one partition.  Groups are runs of adjacent equal keys; sortedness is
+    not checked.  Returns a Groups object."""
+    d, o, k, cnt = segment
+    seg = TzsSegment()
+    seg.d_data = d if isinstance(d, int) or d is None else d.value
+    seg.d_off = o if isinstance(o, int) or o is None else o.value
+    seg.d_klen = k if isinstance(k, int) or k is None else k.value
+    seg.n = cnt
+    g = TzsGroups()
+    _ck(lib().tzs_group_sorted(ctypes.byref(conf), ctypes.byref(seg), ctypes.byref(g)),
+        "group_sorted")
+    return Groups(g)
+
+
+def group_geometry():
+    """(positions per block tile of the flags pass, wide-compare key length
+    or 0) of the grouped reader."""
+    arr = (ctypes.c_uint32 * 2)()
+    lib().tzs_group_geometry(arr)
     return arr[0], arr[1]
 
 

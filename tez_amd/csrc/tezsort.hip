@@ -3256,6 +3256,162 @@ __global__ __launch_bounds__(BLOCK) void k_ifd_gather(
   }
 }
 
+/* ---- grouped reader: CSR key groups over sorted records ----
+ * KeyValuesReader.next()/getCurrentKey()/getCurrentValues() with
+ * ValuesIterator.java:177-199 grouping, as device arrays.  Position i of a
+ * partition's sorted records starts a group iff i == 0 or its serialized key
+ * differs from position i-1's (length first, then bytes): for both
+ * comparators equal-under-the-comparator is equal serialized bytes.
+ *   k_grp_flags  : head flag, head key length, value length per position
+ *   scan_u64 x3  : group ids, key offsets, value offsets (in place)
+ *   k_grp_gather : values, head keys, group_off/key_off                    */
+#define GRP_TILE BLOCK /* positions per block tile of the flags pass */
+#define GRP_WIDE 0     /* key length from which a wide compare applies: none,
+                          the pair compare stays lane-per-pair */
+#ifndef GRP_HALF_AVG
+#define GRP_HALF_AVG 128 /* average copy bytes per position below which the
+                            gather gives a position a half wave */
+#endif
+
+struct GrpKV {
+  const uint8_t* key; /* serialized key; the serialized value follows it */
+  uint32_t klen, vlen;
+};
+/* rt_view without the content decode (no read of the key's first byte) */
+__device__ __forceinline__ GrpKV d_grp_view(const RecTable& rt, uint32_t g) {
+  const uint8_t* data;
+  const uint64_t* off;
+  const uint32_t* klen;
+  uint32_t rec_u, klen_u, r;
+  if (rt.nspills == 1 || g < rt.n0) {
+    data = rt.data0; off = rt.off0; klen = rt.klen0;
+    rec_u = rt.rec_u0; klen_u = rt.klen_u0; r = g;
+  } else {
+    int s = rt_spill_of(rt, g);
+    SegDesc sd = rt.segs[s];
+    data = sd.data; off = sd.off; klen = sd.klen;
+    rec_u = sd.rec_u; klen_u = sd.klen_u; r = g - rt.base[s];
+  }
+  GrpKV v;
+  if (rec_u) {
+    v.key = data + (uint64_t)r * rec_u;
+    v.klen = klen_u;
+    v.vlen = rec_u - klen_u;
+  } else {
+    uint64_t o = off[r];
+    v.key = data + o;
+    v.klen = klen[r];
+    v.vlen = (uint32_t)(off[r + 1] - o - v.klen);
+  }
+  return v;
+}
+
+/* equal-length keys: 8 bytes at a time while both keys hold a whole word
+ * (the loads cover key bytes only), then the byte tail */
+__device__ __forceinline__ bool d_grp_key_equal(const uint8_t* a, const uint8_t* b,
+                                                uint32_t len) {
+  uint32_t i = 0;
+  for (; i + 8 <= len; i += 8) {
+    uint64_t x, y;
+    __builtin_memcpy(&x, a + i, 8);
+    __builtin_memcpy(&y, b + i, 8);
+    if (x != y) return false;
+  }
+  for (; i < len; i++)
+    if (a[i] != b[i]) return false;
+  return true;
+}
+
+/* one position per thread, GRP_TILE positions per tile: every thread stages
+ * its own (key, klen) in LDS so the neighbour's record table lookup is not
+ * repeated; thread 0 also stages the position before the tile. */
+__global__ __launch_bounds__(BLOCK) void k_grp_flags(
+    RecTable rt, const uint32_t* sidx /* partition's positions, null = identity */,
+    uint32_t n, uint64_t* head, uint64_t* klen_head, uint64_t* vlen) {
+  __shared__ const uint8_t* s_key[GRP_TILE + 1];
+  __shared__ uint32_t s_klen[GRP_TILE + 1];
+  const uint32_t ntiles = (uint32_t)(((uint64_t)n + GRP_TILE - 1) / GRP_TILE);
+  const uint32_t t = threadIdx.x;
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint64_t i64 = (uint64_t)tile * GRP_TILE + t;
+    const bool in = i64 < n;
+    const uint32_t i = (uint32_t)i64;
+    GrpKV v = {nullptr, 0, 0};
+    if (in) v = d_grp_view(rt, sidx ? sidx[i] : i);
+    s_key[t + 1] = v.key;
+    s_klen[t + 1] = v.klen;
+    if (t == 0 && tile > 0) {
+      GrpKV p = d_grp_view(rt, sidx ? sidx[i - 1] : i - 1);
+      s_key[0] = p.key;
+      s_klen[0] = p.klen;
+    }
+    __syncthreads();
+    if (in) {
+      bool h = true;
+      if (i > 0) /* length before bytes */
+        h = !(s_klen[t] == v.klen && d_grp_key_equal(s_key[t], v.key, v.klen));
+      head[i] = h ? 1 : 0;
+      klen_head[i] = h ? v.klen : 0;
+      vlen[i] = v.vlen;
+    }
+    __syncthreads();
+  }
+}
+
+/* G lanes copy one byte run.  Long runs: bytes up to a 16-byte aligned
+ * destination, then one 16-byte store per lane, the source read as two
+ * 8-byte loads of the run's own bytes (nothing outside the run is touched). */
+template <int G>
+__device__ __forceinline__ void d_grp_copy(uint8_t* dst, const uint8_t* src,
+                                           uint32_t len, uint32_t lane) {
+  if (len < 96) {
+    for (uint32_t b = lane; b < len; b += G) dst[b] = src[b];
+    return;
+  }
+  uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
+  if (lane < head) dst[lane] = src[lane];
+  dst += head; src += head; len -= head;
+  const uint32_t nv = len >> 4;
+  for (uint32_t v = lane; v < nv; v += G) {
+    const uint8_t* s = src + 16ull * v;
+    uint64_t a, b;
+    __builtin_memcpy(&a, s, 8);
+    __builtin_memcpy(&b, s + 8, 8);
+    *(uint4*)(dst + 16ull * v) = make_uint4((uint32_t)a, (uint32_t)(a >> 32),
+                                            (uint32_t)b, (uint32_t)(b >> 32));
+  }
+  uint32_t tail = len & 15;
+  if (lane < tail) dst[16ull * nv + lane] = src[16ull * nv + lane];
+}
+
+/* G lanes (a wave, or a half wave for short records) per position: the value
+ * goes to val_data; a head also copies its key and writes its group's row of
+ * group_off/key_off.  gid/koff/voff are the exclusive scans of the flags
+ * pass, so position i is a head iff the group id moves on after it. */
+template <int G>
+__global__ __launch_bounds__(BLOCK) void k_grp_gather(
+    RecTable rt, const uint32_t* sidx, uint32_t n, uint64_t n_groups,
+    const uint64_t* gid, const uint64_t* koff, const uint64_t* voff,
+    uint8_t* val_data, uint8_t* key_data, uint64_t* group_off, uint64_t* key_off) {
+  const uint32_t lane = threadIdx.x & (G - 1);
+  const uint64_t nsub = ((uint64_t)gridDim.x * blockDim.x) / G;
+  for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G; i < n;
+       i += nsub) {
+    GrpKV v = d_grp_view(rt, sidx ? sidx[i] : (uint32_t)i);
+    d_grp_copy<G>(val_data + voff[i], v.key + v.klen, v.vlen, lane);
+    const uint64_t g = gid[i];
+    const uint64_t gnext = (i + 1 < n) ? gid[i + 1] : n_groups;
+    if (gnext != g) {
+      const uint64_t ko = koff[i];
+      d_grp_copy<G>(key_data + ko, v.key, v.klen, lane);
+      if (lane == 0) {
+        group_off[g] = i;
+        key_off[g] = ko;
+      }
+    }
+  }
+}
+
 /* ================================================================== */
 /* host-side engine                                                    */
 /* ================================================================== */
@@ -6157,6 +6313,114 @@ extern "C" int tzs_sorter_add_ifile_segment(tzs_sorter* s, const void* d_bytes,
   sp->off = std::move(off);
   sp->klen = std::move(klen);
   return rc;
+}
+
+/* ---- grouped reader -------------------------------------
+ * Scratch is pool memory released on return: 16 bytes per record (head
+ * flags and head key lengths, each scanned in place).  The value lengths are
+ * scanned in place inside the d_val_off output. */
+static int group_impl(const RecTable& rt, const uint32_t* d_sidx, uint32_t n,
+                      tzs_groups* out) {
+  DBuf gid, koff, voff, goff, okoff, kdata, vdata;
+  if (gid.alloc(8ull * n)) return -12;
+  if (koff.alloc(8ull * n)) return -12;
+  if (voff.alloc(8ull * ((uint64_t)n + 1))) return -12;
+  uint32_t ntiles = (uint32_t)(((uint64_t)n + GRP_TILE - 1) / GRP_TILE);
+  hipLaunchKernelGGL(k_grp_flags, dim3(ntiles > 2048 ? 2048 : ntiles), dim3(BLOCK), 0, 0,
+                     rt, d_sidx, n, (uint64_t*)gid.p, (uint64_t*)koff.p,
+                     (uint64_t*)voff.p);
+  uint64_t G = 0, kbytes = 0, vbytes = 0;
+  int rc;
+  if ((rc = scan_u64((uint64_t*)gid.p, (uint64_t*)gid.p, n, &G))) return rc;
+  if ((rc = scan_u64((uint64_t*)koff.p, (uint64_t*)koff.p, n, &kbytes))) return rc;
+  if ((rc = scan_u64((uint64_t*)voff.p, (uint64_t*)voff.p, n, &vbytes))) return rc;
+  if (G == 0 || G > n) FAIL(-70, "grouped: bad group count %llu", (unsigned long long)G);
+  if (goff.alloc(8ull * (G + 1))) return -12;
+  if (okoff.alloc(8ull * (G + 1))) return -12;
+  if (kdata.alloc(kbytes ? kbytes : 1)) return -12;
+  if (vdata.alloc(vbytes ? vbytes : 1)) return -12;
+  uint64_t n64 = n;
+  HIP_CHECK(hipMemcpy((uint64_t*)voff.p + n, &vbytes, 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy((uint64_t*)goff.p + G, &n64, 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy((uint64_t*)okoff.p + G, &kbytes, 8, hipMemcpyHostToDevice));
+  /* a half wave per position when the average copy is short */
+  const bool half = (vbytes + kbytes) / n < GRP_HALF_AVG;
+  const uint32_t per_block = half ? BLOCK / 32 : WPB;
+  uint64_t nb = ((uint64_t)n + per_block - 1) / per_block;
+  if (nb > 2048) nb = 2048;
+  if (half)
+    hipLaunchKernelGGL((k_grp_gather<32>), dim3((uint32_t)nb), dim3(BLOCK), 0, 0, rt,
+                       d_sidx, n, G, (const uint64_t*)gid.p, (const uint64_t*)koff.p,
+                       (const uint64_t*)voff.p, (uint8_t*)vdata.p, (uint8_t*)kdata.p,
+                       (uint64_t*)goff.p, (uint64_t*)okoff.p);
+  else
+    hipLaunchKernelGGL((k_grp_gather<WAVE>), dim3((uint32_t)nb), dim3(BLOCK), 0, 0, rt,
+                       d_sidx, n, G, (const uint64_t*)gid.p, (const uint64_t*)koff.p,
+                       (const uint64_t*)voff.p, (uint8_t*)vdata.p, (uint8_t*)kdata.p,
+                       (uint64_t*)goff.p, (uint64_t*)okoff.p);
+  HIP_CHECK(hipDeviceSynchronize());
+  out->n_records = (int64_t)n;
+  out->n_groups = (int64_t)G;
+  out->d_group_off = (uint64_t*)dbuf_export(goff);
+  out->d_key_data = dbuf_export(kdata);
+  out->d_key_off = (uint64_t*)dbuf_export(okoff);
+  out->d_val_data = dbuf_export(vdata);
+  out->d_val_off = (uint64_t*)dbuf_export(voff);
+  return 0;
+}
+
+extern "C" void tzs_group_geometry(uint32_t out[2]) {
+  out[0] = GRP_TILE;
+  out[1] = GRP_WIDE;
+}
+
+extern "C" int tzs_sorter_grouped(tzs_sorter* s, int32_t partition, tzs_groups* out) {
+  if (!s) FAIL(-22, "grouped: null sorter");
+  if (!out) FAIL(-22, "grouped: null output");
+  memset(out, 0, sizeof(*out));
+  if (partition < 0 || partition >= s->conf.num_partitions)
+    FAIL(-22, "grouped: partition %d out of range [0, %d)", partition,
+         s->conf.num_partitions);
+  if (!s->flushed) FAIL(-22, "grouped: flush first");
+  if ((int)s->final_index.size() != s->conf.num_partitions)
+    FAIL(-22, "grouped: no merged record set (final merge disabled with %d spills)",
+         (int)s->spills.size());
+  if (s->final_n == 0 || (int)s->final_rec_ranges.size() != s->conf.num_partitions + 1)
+    return 0; /* nothing was written */
+  uint64_t r0 = s->final_rec_ranges[partition], r1 = s->final_rec_ranges[partition + 1];
+  if (r1 > s->final_n || r0 > r1) FAIL(-70, "grouped: inconsistent partition ranges");
+  if (r0 == r1) return 0;
+  return group_impl(s->final_rt, (const uint32_t*)s->sidx.p + r0, (uint32_t)(r1 - r0), out);
+}
+
+extern "C" int tzs_group_sorted(const tzs_conf* conf, const tzs_segment* seg,
+                                tzs_groups* out) {
+  if (!conf) FAIL(-22, "group_sorted: null conf");
+  if (!seg) FAIL(-22, "group_sorted: null segment");
+  if (!out) FAIL(-22, "group_sorted: null output");
+  memset(out, 0, sizeof(*out));
+  if (seg->n < 0) FAIL(-22, "group_sorted: negative n");
+  if (seg->n > 0 && (!seg->d_data || !seg->d_off || !seg->d_klen))
+    FAIL(-22, "group_sorted: null columns with n > 0");
+  if (seg->n > 4000000000ll) FAIL(-22, "group_sorted: segment too large (u32 record ids)");
+  if (seg->n == 0) return 0;
+  RecTable rt = {};
+  rt.nspills = 1;
+  rt.data0 = (const uint8_t*)seg->d_data;
+  rt.off0 = seg->d_off;
+  rt.klen0 = seg->d_klen;
+  rt.n0 = (uint32_t)seg->n;
+  rt.key_type = conf->key_type;
+  return group_impl(rt, nullptr, (uint32_t)seg->n, out);
+}
+
+extern "C" void tzs_groups_free(tzs_groups* g) {
+  if (!g) return;
+  pool_free_raw(g->d_group_off); g->d_group_off = nullptr;
+  pool_free_raw(g->d_key_data);  g->d_key_data = nullptr;
+  pool_free_raw(g->d_key_off);   g->d_key_off = nullptr;
+  pool_free_raw(g->d_val_data);  g->d_val_data = nullptr;
+  pool_free_raw(g->d_val_off);   g->d_val_off = nullptr;
 }
 
 /* ---- misc helpers for the Python layer ---- */
