@@ -331,3 +331,31 @@ def test_parity_variable_length_bytes_keys(engine):
     want = _oracle_single_spill(pairs, 8, o.KEY_BYTES, o.CMP_TEZBYTES)
     assert gidx == o.index_decode(want["index"], 8)
     assert got == want["data"]
+
+
+def test_parity_records_longer_than_128_bytes(engine):
+    """k_emit_records' per-record loop.  P=1, 133 = 2*64 + 5 records; the key
+    content is a 4-byte big-endian rank plus 8 random bytes, so record r
+    lands at sorted position r.  Positions 0..63: key + value of at most
+    116 B, a full wave on the pipelined branch.  Positions 64..127: one
+    record of exactly 129 B (key + value) and one with a 300-byte value, a
+    full wave that must take the per-record loop.  128..132: the partial last
+    wave, which always does."""
+    rng = random.Random(133)
+    vlens = {r: rng.randrange(0, 97) for r in range(133)}
+    vlens[70] = 129 - 16 - 4   # 16 B serialized key + 4 B value length word
+    vlens[100] = 300
+    pairs = []
+    for r in range(133):
+        k = r.to_bytes(4, "big") + bytes(rng.randrange(256) for _ in range(8))
+        v = bytes(rng.randrange(256) for _ in range(vlens[r]))
+        pairs.append((o.serialize_bytes_writable(k), o.serialize_bytes_writable(v)))
+    lens = [len(k) + len(v) for k, v in pairs]
+    assert max(lens[:64]) <= 128 and lens[70] == 129 and lens[100] == 320
+    assert max(lens[128:]) <= 128
+    rng.shuffle(pairs)
+    got, gidx, _ = _run_engine_host_path(engine, pairs, 1, engine.KEY_BYTES,
+                                         engine.CMP_TEZBYTES)
+    want = _oracle_single_spill(pairs, 1, o.KEY_BYTES, o.CMP_TEZBYTES)
+    assert gidx == o.index_decode(want["index"], 1)
+    assert got == want["data"]

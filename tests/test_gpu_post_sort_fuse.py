@@ -4,9 +4,8 @@ k_crc_chunks (four units, one per wave, to a 16 KiB super-chunk), folded per
 range by k_crc_combine_ranges.
 
 Every case compares the IFile stream and the index byte for byte with the
-CPU oracle.  Cases that reach the metadata kernel or the compaction run
-twice, on the default path and with TZS_POST_FUSE=0 (the separate
-k_eq_init / k_count_nonzero_u8 / k_part_hist passes, no tile skip).
+CPU oracle.  The metadata kernel and the tile skip are the only path: the
+separate passes they replaced, and the switch that selected them, are gone.
 
 Shapes sit on the edges of SCAN_TILE = 2048 positions, of the 4096-byte CRC
 unit and of the 16384-byte CRC super-chunk."""
@@ -32,16 +31,6 @@ def engine():
     if not tez_amd.device_available():
         pytest.skip("no GPU")
     return tez_amd
-
-
-def _toggles(monkeypatch):
-    """Default path first, then TZS_POST_FUSE=0."""
-    for toggle in (None, "0"):
-        if toggle is None:
-            monkeypatch.delenv("TZS_POST_FUSE", raising=False)
-        else:
-            monkeypatch.setenv("TZS_POST_FUSE", toggle)
-        yield toggle
 
 
 def _records_from_keys(keys, vlen, seed):
@@ -89,37 +78,36 @@ def _sort_uploaded(engine, data, offs, klens, P, parts=None, **conf_kw):
     return got
 
 
-def _check_both_paths(engine, monkeypatch, data, offs, klens, P, parts=None):
+def _check(engine, data, offs, klens, P, parts=None):
     want = o.spill(data, offs, klens, P, key_type=o.KEY_BYTES,
                    comparator=o.CMP_TEZBYTES, partitions=parts)
     want_index = o.index_decode(want["index"], P)
-    for toggle in _toggles(monkeypatch):
-        got, gidx = _sort_uploaded(engine, data, offs, klens, P, parts)
-        assert gidx == want_index, f"index, TZS_POST_FUSE={toggle}"
-        assert got == want["data"], f"stream, TZS_POST_FUSE={toggle}"
+    got, gidx = _sort_uploaded(engine, data, offs, klens, P, parts)
+    assert gidx == want_index, "index"
+    assert got == want["data"], "stream"
     return want, want_index
 
 
 # ---- tile edges and partition starts -------------------------------------
 
 @pytest.mark.parametrize("n", [1, 2, 2047, 2048, 2049, 4097])
-def test_tile_edges(engine, monkeypatch, n):
+def test_tile_edges(engine, n):
     """P=64, 88-byte records.  n = 1 and 2 leave nearly every partition
     empty (leading, trailing and interior gaps in the partition starts); the
     others put the last position just inside, on and just past a tile."""
     data, offs, klens = _records_from_keys(_unique_keys(n, 16, 300 + n), 64,
                                            seed=400 + n)
-    _check_both_paths(engine, monkeypatch, data, offs, klens, 64)
+    _check(engine, data, offs, klens, 64)
 
 
 @pytest.mark.parametrize("P", [1, 2, 3, 199])
-def test_partition_counts(engine, monkeypatch, P):
+def test_partition_counts(engine, P):
     """P=1 has no partition bits in the composite; 3 and 199 are no powers
     of two (199 > the records of some tiles' partitions: empty ones occur)."""
     n = 3001
     data, offs, klens = _records_from_keys(_unique_keys(n, 16, 500 + P), 64,
                                            seed=600 + P)
-    _check_both_paths(engine, monkeypatch, data, offs, klens, P)
+    _check(engine, data, offs, klens, P)
 
 
 def _explicit_parts(kind, n):
@@ -138,7 +126,7 @@ def _explicit_parts(kind, n):
 
 @pytest.mark.parametrize("kind", ["all_last", "all_first", "first_and_last",
                                   "boundary_on_tile_edge"])
-def test_explicit_partitions(engine, monkeypatch, kind):
+def test_explicit_partitions(engine, kind):
     """n = 4101, P = 16, caller-supplied partitions: every record in the
     last partition (15 leading empties), in the first (15 trailing), only in
     0 and 15 (14 interior empties filled from one position), and a 0/1
@@ -146,13 +134,13 @@ def test_explicit_partitions(engine, monkeypatch, kind):
     n, P = 4101, 16
     data, offs, klens = _records_from_keys(_unique_keys(n, 16, 700), 64,
                                            seed=701)
-    _check_both_paths(engine, monkeypatch, data, offs, klens, P,
+    _check(engine, data, offs, klens, P,
                       _explicit_parts(kind, n))
 
 
 # ---- ties, tile skip, refinement levels ----------------------------------
 
-def test_equal_run_across_tile_edge(engine, monkeypatch):
+def test_equal_run_across_tile_edge(engine):
     """P=1, n=4100: key i is the integer i, except that 2040..2055 all carry
     2040, so one run of 16 fully equal keys occupies sorted positions
     2040..2055 over the first tile edge (eq lookahead and in-run counts on
@@ -164,11 +152,11 @@ def test_equal_run_across_tile_edge(engine, monkeypatch):
     _be_prefix(keys, ids, 4)
     keys = keys[np.random.default_rng(9).permutation(n)]
     data, offs, klens = _records_from_keys(keys, 64, seed=10)
-    want, _ = _check_both_paths(engine, monkeypatch, data, offs, klens, 1)
+    want, _ = _check(engine, data, offs, klens, 1)
     assert want["rle"] == 0
 
 
-def test_equal_pairs_turn_writer_rle_on(engine, monkeypatch):
+def test_equal_pairs_turn_writer_rle_on(engine):
     """P=1, n=4100, every key twice: 2050 equal pairs, well over a tenth of
     n, so the eq count that now comes from the metadata kernel must switch
     the writer's RLE on."""
@@ -177,11 +165,11 @@ def test_equal_pairs_turn_writer_rle_on(engine, monkeypatch):
     _be_prefix(keys, np.arange(n, dtype=np.int64) // 2 * 7919, 4)
     keys = keys[np.random.default_rng(11).permutation(n)]
     data, offs, klens = _records_from_keys(keys, 64, seed=12)
-    want, _ = _check_both_paths(engine, monkeypatch, data, offs, klens, 1)
+    want, _ = _check(engine, data, offs, klens, 1)
     assert want["rle"] == 1
 
 
-def test_skipped_tiles_between_live_ones(engine, monkeypatch):
+def test_skipped_tiles_between_live_ones(engine):
     """P=1, n = 3*2048 + 56: the composite covers the first 3 key bytes at
     this n.  Only the 5 smallest and the 6 largest keys share those bytes
     (two of the largest are fully equal); every key between is alone.  Tile
@@ -197,10 +185,10 @@ def test_skipped_tiles_between_live_ones(engine, monkeypatch):
     keys[n - 1] = keys[n - 2]
     keys = keys[rng.permutation(n)]
     data, offs, klens = _records_from_keys(keys, 64, seed=22)
-    _check_both_paths(engine, monkeypatch, data, offs, klens, 1)
+    _check(engine, data, offs, klens, 1)
 
 
-def test_multi_level_refinement(engine, monkeypatch):
+def test_multi_level_refinement(engine):
     """P=1, 16-byte keys.  Groups of 4 share their first 12 bytes and differ
     in the last 4, so they survive level 0 (bytes 3..10) and split at level
     1; in every sixth group two keys are fully equal and go on to the length
@@ -227,13 +215,13 @@ def test_multi_level_refinement(engine, monkeypatch):
     keys = np.concatenate([gkeys, skeys])
     keys = keys[rng.permutation(len(keys))]
     data, offs, klens = _records_from_keys(keys, 24, seed=32)
-    _check_both_paths(engine, monkeypatch, data, offs, klens, 1)
+    _check(engine, data, offs, klens, 1)
 
 
 # ---- merge entry (lo keys given) -----------------------------------------
 
 @pytest.mark.parametrize("sizes", [(1000, 1100), (1500, 1500, 1150)])
-def test_merge_entry(engine, monkeypatch, sizes):
+def test_merge_entry(engine, sizes):
     """Two and three spills, then flush, P=4: the merge hands the lo keys
     to the metadata kernel.  Keys repeat within and across spills; the
     totals (2100, 4150) straddle one and two tiles."""
@@ -252,24 +240,23 @@ def test_merge_entry(engine, monkeypatch, sizes):
         spills.append(o.spill(d, f, kl, P))
     want = o.final_merge(spills, P)
     want_index = o.index_decode(want["index"], P)
-    for toggle in _toggles(monkeypatch):
-        s = engine.Sorter(engine.make_conf(P, key_type=engine.KEY_BYTES,
-                                           comparator=engine.CMP_TEZBYTES))
-        for batch in batches:
-            for k, v in batch:
-                s.write(k, v, -1)
-            s.spill()
-        assert s.num_spills() == len(sizes)
-        s.flush()
-        got, gidx = s.output()
-        s.close()
-        assert gidx == want_index, f"index, TZS_POST_FUSE={toggle}"
-        assert got == want["data"], f"stream, TZS_POST_FUSE={toggle}"
+    s = engine.Sorter(engine.make_conf(P, key_type=engine.KEY_BYTES,
+                                       comparator=engine.CMP_TEZBYTES))
+    for batch in batches:
+        for k, v in batch:
+            s.write(k, v, -1)
+        s.spill()
+    assert s.num_spills() == len(sizes)
+    s.flush()
+    got, gidx = s.output()
+    s.close()
+    assert gidx == want_index, "index"
+    assert got == want["data"], "stream"
 
 
 # ---- combiner: partition counts after the view was replaced --------------
 
-def test_combiner_single_spill(engine, monkeypatch):
+def test_combiner_single_spill(engine):
     """SUM_INT combiner: the fold replaces n and the partition array, so the
     partition counts come from k_part_hist, not from the starts taken before
     the fold."""
@@ -283,17 +270,16 @@ def test_combiner_single_spill(engine, monkeypatch):
     want = o.spill(d, f, kl, P, key_type=o.KEY_TEXT, comparator=o.CMP_TEXT,
                    combiner=1)
     want_index = o.index_decode(want["index"], P)
-    for toggle in _toggles(monkeypatch):
-        s = engine.Sorter(engine.make_conf(P, key_type=engine.KEY_TEXT,
-                                           comparator=engine.CMP_TEXT,
-                                           combiner=1))
-        for k, v in pairs:
-            s.write(k, v, -1)
-        s.flush()
-        got, gidx = s.output()
-        s.close()
-        assert gidx == want_index, f"index, TZS_POST_FUSE={toggle}"
-        assert got == want["data"], f"stream, TZS_POST_FUSE={toggle}"
+    s = engine.Sorter(engine.make_conf(P, key_type=engine.KEY_TEXT,
+                                       comparator=engine.CMP_TEXT,
+                                       combiner=1))
+    for k, v in pairs:
+        s.write(k, v, -1)
+    s.flush()
+    got, gidx = s.output()
+    s.close()
+    assert gidx == want_index, "index"
+    assert got == want["data"], "stream"
 
 
 # ---- CRC lengths and byte phases -----------------------------------------
@@ -382,7 +368,7 @@ def test_crc_range_over_256_units(engine, n):
 
 # ---- the benchmark's route -----------------------------------------------
 
-def test_adopted_generated_batch(engine, monkeypatch):
+def test_adopted_generated_batch(engine):
     """Device-generated 88-byte records handed over with
     write_batch_device_adopt, n = 300,000 and P = 64: about 150 tiles and
     about 25 super-chunks per partition."""
@@ -390,23 +376,20 @@ def test_adopted_generated_batch(engine, monkeypatch):
     n, P, klen, vlen = 300_000, 64, 16, 64
     rec = 8 + klen + vlen
     conf = engine.make_conf(P)
-    want = want_index = None
-    for toggle in _toggles(monkeypatch):
-        d, off, kl, part = engine.generate(seed=0xF05E, n=n, kind=0, klen=klen,
-                                           vlen=vlen, conf=conf)
-        if want is None:
-            data = np.zeros(rec * n, dtype=np.uint8)
-            _ck(lib().tzs_memcpy_d2h(data.ctypes.data, d, rec * n), "d2h")
-            offs = np.arange(0, rec * (n + 1), rec, dtype=np.uint64)
-            klens = np.full(n, 4 + klen, dtype=np.uint32)
-            want = o.spill(data, offs, klens, P, key_type=o.KEY_BYTES,
-                           comparator=o.CMP_TEZBYTES)
-            want_index = o.index_decode(want["index"], P)
-        engine.free_device(part)
-        s = engine.Sorter(conf)
-        s.write_batch_device_adopt(d, off, kl, None, n)
-        s.flush()
-        got, gidx = s.output()
-        s.close()
-        assert gidx == want_index, f"index, TZS_POST_FUSE={toggle}"
-        assert got == want["data"], f"stream, TZS_POST_FUSE={toggle}"
+    d, off, kl, part = engine.generate(seed=0xF05E, n=n, kind=0, klen=klen,
+                                       vlen=vlen, conf=conf)
+    data = np.zeros(rec * n, dtype=np.uint8)
+    _ck(lib().tzs_memcpy_d2h(data.ctypes.data, d, rec * n), "d2h")
+    offs = np.arange(0, rec * (n + 1), rec, dtype=np.uint64)
+    klens = np.full(n, 4 + klen, dtype=np.uint32)
+    want = o.spill(data, offs, klens, P, key_type=o.KEY_BYTES,
+                   comparator=o.CMP_TEZBYTES)
+    want_index = o.index_decode(want["index"], P)
+    engine.free_device(part)
+    s = engine.Sorter(conf)
+    s.write_batch_device_adopt(d, off, kl, None, n)
+    s.flush()
+    got, gidx = s.output()
+    s.close()
+    assert gidx == want_index, "index"
+    assert got == want["data"], "stream"

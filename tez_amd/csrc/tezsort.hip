@@ -125,15 +125,6 @@ extern "C" uint32_t tzs_test_crc32(uint32_t c, const void* p, uint64_t n) {
   return h_crc32(c, (const uint8_t*)p, n);
 }
 
-/* hadoop vint (WritableUtils) — host side for tiny patches */
-static int h_vint_size(int64_t i) {
-  if (i >= -112 && i <= 127) return 1;
-  if (i < 0) i = ~i;
-  int n = 0;
-  while (i != 0) { i = (int64_t)((uint64_t)i >> 8); n++; }
-  return n + 1;
-}
-
 /* ------------------------------------------------------------------ */
 /* device helpers                                                      */
 /* ------------------------------------------------------------------ */
@@ -309,7 +300,14 @@ __global__ void k_hash_partition(RecTable rt, int32_t P, int32_t* d_part, uint32
 /* composite = (part << (64-pbits)) | (first content bytes BE >> pbits),
  * masked to the top sort_bytes bytes: the radix sort only orders those
  * (adaptive pass count — DESIGN.md §4); rarer-than-1% ties are resolved by
- * the refinement levels, whose equality test must see the same mask. */
+ * the refinement levels, whose equality test must see the same mask.
+ * d_part == nullptr: compute the HashPartitioner placement here (fused —
+ * a separate hash kernel re-reads all content bytes, ~10 GB at n=1e8).
+ * ser_mode (TezBytesComparator): order = partition, 3-byte content proxy,
+ * then the SERIALIZED key bytes (4B BE length first => length-then-content
+ * ties) — the reference prefix-int + raw-compare order
+ * (PipelinedSorter.java:451-463, TezBytesComparator.java:38-62).
+ * !ser_mode (Text): partition then content bytes, shorter-first ties. */
 __device__ __forceinline__ uint64_t d_composite_one(
     const RecTable& rt, const int32_t* d_part, int32_t P, int pbits,
     int ref_pb, int ser_mode, uint64_t mask, uint32_t i) {
@@ -319,10 +317,13 @@ __device__ __forceinline__ uint64_t d_composite_one(
   else part = (uint32_t)((d_hash_bytes(v.content, (int32_t)v.clen) & 0x7fffffff) % P);
   uint64_t key;
   if (ser_mode) {
+    /* the reference prefix keeps only proxy >>> (bitcount(P)+1) bits
+       (PipelinedSorter.java:457): ties on the TRUNCATED proxy fall through
+       to the serialized compare, so the composite must truncate too */
     uint32_t proxy = ((v.clen > 0 ? (uint32_t)v.content[0] : 0u) << 16) |
                      ((v.clen > 1 ? (uint32_t)v.content[1] : 0u) << 8) |
                      (v.clen > 2 ? (uint32_t)v.content[2] : 0u);
-    int pw = 24 - ref_pb;
+    int pw = 24 - ref_pb;            /* surviving proxy bits */
     if (pw < 0) pw = 0;
     uint32_t proxy_t = pw ? (proxy >> (24 - pw)) : 0;
     uint64_t ser = 0;
@@ -443,44 +444,10 @@ __global__ __launch_bounds__(BLOCK) void k_build_composite_stream(
 __global__ void k_build_composite(RecTable rt, const int32_t* d_part, int32_t P,
                                   int pbits, int ref_pb, int sort_bytes, int ser_mode,
                                   uint64_t* d_key, uint32_t* d_idx, uint32_t n) {
-  /* d_part == nullptr: compute the HashPartitioner placement here (fused —
-     a separate hash kernel re-reads all content bytes, ~10 GB at n=1e8).
-     ser_mode (TezBytesComparator): order = partition, 3-byte content proxy,
-     then the SERIALIZED key bytes (4B BE length first => length-then-content
-     ties) — the reference prefix-int + raw-compare order
-     (PipelinedSorter.java:451-463, TezBytesComparator.java:38-62).
-     !ser_mode (Text): partition then content bytes, shorter-first ties. */
   uint64_t mask = (sort_bytes >= 8) ? ~0ull : ~0ull << (8 * (8 - sort_bytes));
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * blockDim.x) {
-    RecView v = rt_view(rt, i);
-    uint32_t part;
-    if (d_part) part = (uint32_t)d_part[i];
-    else part = (uint32_t)((d_hash_bytes(v.content, (int32_t)v.clen) & 0x7fffffff) % P);
-    uint64_t key;
-    if (ser_mode) {
-      /* the reference prefix keeps only proxy >>> (bitcount(P)+1) bits
-         (PipelinedSorter.java:457): ties on the TRUNCATED proxy fall through
-         to the serialized compare, so the composite must truncate too */
-      uint32_t proxy = ((v.clen > 0 ? (uint32_t)v.content[0] : 0u) << 16) |
-                       ((v.clen > 1 ? (uint32_t)v.content[1] : 0u) << 8) |
-                       (v.clen > 2 ? (uint32_t)v.content[2] : 0u);
-      int pw = 24 - ref_pb;            /* surviving proxy bits */
-      if (pw < 0) pw = 0;
-      uint32_t proxy_t = pw ? (proxy >> (24 - pw)) : 0;
-      uint64_t ser = 0;
-      uint32_t m = v.klen < 8 ? v.klen : 8;
-      for (uint32_t b = 0; b < m; b++) ser |= (uint64_t)v.key[b] << (56 - 8 * b);
-      key = ((uint64_t)part << (64 - pbits))
-            | ((uint64_t)proxy_t << (64 - pbits - pw))
-            | (ser >> (pbits + pw));
-    } else {
-      uint64_t c = 0;
-      uint32_t m = v.clen < 8 ? v.clen : 8;
-      for (uint32_t b = 0; b < m; b++) c |= (uint64_t)v.content[b] << (56 - 8 * b);
-      key = pbits ? (((uint64_t)part << (64 - pbits)) | (c >> pbits)) : c;
-    }
-    d_key[i] = key & mask;
+    d_key[i] = d_composite_one(rt, d_part, P, pbits, ref_pb, ser_mode, mask, i);
     d_idx[i] = i;
   }
 }
@@ -489,15 +456,14 @@ __global__ void k_build_composite(RecTable rt, const int32_t* d_part, int32_t P,
  * hist: per-block digit counts over its contiguous tile.
  * scan: off[b][d] = digit_base[d] + sum_{b'<b} cnt[b'][d]  (digit-major scan)
  * scatter: stable rank within tile via wave ballots + LDS wave histograms. */
-template <typename KeyT, int BLK = BLOCK>
+template <typename KeyT>
 __global__ void k_radix_hist(const KeyT* keys, uint32_t n, int byte_idx,
                              uint32_t* counts /* [nblocks*RADIX] */) {
-  constexpr uint32_t OT = (uint32_t)TILE_ROUNDS * BLK;
   __shared__ uint32_t h[RADIX];
   for (int i = threadIdx.x; i < RADIX; i += blockDim.x) h[i] = 0;
   __syncthreads();
-  uint32_t start = blockIdx.x * OT;
-  uint32_t end = min(start + OT, n);
+  uint32_t start = blockIdx.x * TILE;
+  uint32_t end = min(start + TILE, n);
   for (uint32_t i = start + threadIdx.x; i < end; i += blockDim.x) {
     uint32_t d = (uint32_t)(keys[i] >> (8 * byte_idx)) & 0xFF;
     atomicAdd(&h[d], 1u);
@@ -559,32 +525,30 @@ __global__ void k_radix_scan_digits(uint32_t* totals, uint32_t* bases) {
  * region is re-used for the key staging (consumed into registers first).
  * Stores stay digit-contiguous (partial-line scatter waste was the round-1
  * fix). */
-template <typename KeyT, bool HAS_A1, bool HAS_B64 = false, int BLK = BLOCK>
-__global__ __launch_bounds__(BLK) void k_radix_scatter(
+template <typename KeyT, bool HAS_A1, bool HAS_B64 = false>
+__global__ __launch_bounds__(BLOCK) void k_radix_scatter(
     const KeyT* keys_in, KeyT* keys_out,
     const uint32_t* a0_in, uint32_t* a0_out,
     const uint32_t* a1_in, uint32_t* a1_out,
     const uint64_t* b64_in, uint64_t* b64_out,
     uint32_t n, int byte_idx,
     const uint32_t* offsets, const uint32_t* bases) {
-  constexpr uint32_t OT = (uint32_t)TILE_ROUNDS * BLK;
-  constexpr int OWPB = BLK / WAVE;
-  constexpr int RW = OWPB * TILE_ROUNDS;
+  constexpr int RW = WPB * TILE_ROUNDS;
   constexpr size_t CNT_BYTES = (size_t)RW * RADIX * 2;
-  constexpr size_t KEY_BYTES = (size_t)OT * sizeof(KeyT);
+  constexpr size_t KEY_BYTES = (size_t)TILE * sizeof(KeyT);
   constexpr size_t UNION_BYTES = CNT_BYTES > KEY_BYTES ? CNT_BYTES : KEY_BYTES;
   __shared__ __attribute__((aligned(16))) uint8_t u_raw[UNION_BYTES];
-  __shared__ uint32_t ls_a0[OT];
-  __shared__ uint32_t ls_a1[HAS_A1 ? OT : 1];
-  __shared__ uint64_t ls_b64[HAS_B64 ? OT : 1];
+  __shared__ uint32_t ls_a0[TILE];
+  __shared__ uint32_t ls_a1[HAS_A1 ? TILE : 1];
+  __shared__ uint64_t ls_b64[HAS_B64 ? TILE : 1];
   __shared__ uint32_t tileoff[RADIX];
   uint16_t* cnt = (uint16_t*)u_raw;
   KeyT* ls_key = (KeyT*)u_raw;
   for (uint32_t i = threadIdx.x; i < (uint32_t)RW * RADIX / 2; i += blockDim.x)
     ((uint32_t*)cnt)[i] = 0;
   __syncthreads();
-  uint32_t start = blockIdx.x * OT;
-  uint32_t end = min(start + OT, n);
+  uint32_t start = blockIdx.x * TILE;
+  uint32_t end = min(start + TILE, n);
   uint32_t count = (start < n) ? (end - start) : 0;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = threadIdx.x / WAVE;
@@ -599,7 +563,7 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter(
      memory latency is paid once per tile, not once per ranking round */
   #pragma unroll
   for (int r = 0; r < TILE_ROUNDS; r++) {
-    uint32_t i = start + (uint32_t)r * BLK + threadIdx.x;
+    uint32_t i = start + (uint32_t)r * BLOCK + threadIdx.x;
     bool active = i < end;
     my_key[r] = active ? keys_in[i] : (KeyT)0;
     my_a0[r] = active ? a0_in[i] : 0;
@@ -607,7 +571,7 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter(
     if (HAS_B64) my_b64[r] = active ? b64_in[i] : 0;
   }
   for (int r = 0; r < TILE_ROUNDS; r++) {
-    uint32_t i = start + (uint32_t)r * BLK + threadIdx.x;
+    uint32_t i = start + (uint32_t)r * BLOCK + threadIdx.x;
     bool active = i < end;
     uint32_t d = active ? ((uint32_t)(my_key[r] >> (8 * byte_idx)) & 0xFF) : 0u;
     uint64_t m = ~0ull;
@@ -619,7 +583,7 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter(
     m &= act;
     uint32_t lane_rank = (uint32_t)__popcll(m & lt_mask);
     if (active && lane_rank == 0)
-      cnt[(r * OWPB + wv) * RADIX + d] = (uint16_t)__popcll(m);
+      cnt[(r * WPB + wv) * RADIX + d] = (uint16_t)__popcll(m);
     my_rank[r] = (uint16_t)lane_rank;
     my_dig[r] = (uint16_t)d;
   }
@@ -654,12 +618,12 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter(
   uint16_t my_slot[TILE_ROUNDS];
   for (int r = 0; r < TILE_ROUNDS; r++) {
     uint32_t d = my_dig[r];
-    my_slot[r] = (uint16_t)(tileoff[d] + cnt[(r * OWPB + wv) * RADIX + d] +
+    my_slot[r] = (uint16_t)(tileoff[d] + cnt[(r * WPB + wv) * RADIX + d] +
                             my_rank[r]);
   }
   __syncthreads(); /* cnt consumed; region becomes the key staging */
   for (int r = 0; r < TILE_ROUNDS; r++) {
-    uint32_t i = start + (uint32_t)r * BLK + threadIdx.x;
+    uint32_t i = start + (uint32_t)r * BLOCK + threadIdx.x;
     if (i < end) {
       uint32_t slot = my_slot[r];
       ls_key[slot] = my_key[r];
@@ -689,8 +653,13 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter(
  * started), tile digit counts are published as single-word agent-scope
  * atomics with a 2-bit status packed in (the guide's data-is-the-flag R2
  * form), and each tile resolves its exclusive prefix by walking back until
- * an INCLUSIVE entry.  Spins are bounded; on timeout an error flag makes the
- * host redo the pass with the classic 3-kernel path. */
+ * an INCLUSIVE entry.  Spins are bounded; on timeout an error flag is raised
+ * and radix_sort fails the sort with -70 (the pass has already scattered
+ * through wrong offsets, so there is nothing to fall back from).
+ * One shape only: key + one u32 payload at 1024 threads = 8192-element tile,
+ * 1 block x 16 waves per CU, digit runs of ~32 x 12 B. */
+#define OS_BLOCK 1024
+#define OS_TILE ((uint32_t)TILE_ROUNDS * OS_BLOCK)
 #define OS_AGG (1u << 30)
 #define OS_INC (2u << 30)
 #define OS_CNT_MASK ((1u << 30) - 1)
@@ -733,12 +702,10 @@ __global__ void k_os_bases(const uint32_t* counts, uint32_t* bases) {
   bases[p * RADIX + d] = tot[d];
 }
 
-template <typename KeyT, bool HAS_A1, bool HAS_B64 = false, int BLK = BLOCK>
-__global__ __launch_bounds__(BLK) void k_onesweep_pass(
+template <typename KeyT>
+__global__ __launch_bounds__(OS_BLOCK) void k_onesweep_pass(
     const KeyT* keys_in, KeyT* keys_out,
     const uint32_t* a0_in, uint32_t* a0_out,
-    const uint32_t* a1_in, uint32_t* a1_out,
-    const uint64_t* b64_in, uint64_t* b64_out,
     uint32_t n, int byte_idx,
     const uint32_t* bases /* [256] exclusive digit bases */,
     uint32_t* status /* [ntiles*256] */, uint32_t* ticket, uint32_t* error) {
@@ -746,16 +713,14 @@ __global__ __launch_bounds__(BLK) void k_onesweep_pass(
    * tiles are ticketed (dispatch order is undefined on CDNA4), per-tile
    * digit totals publish as AGG/INC status words, the lookback overlaps
    * the LDS staging stores. */
-  constexpr uint32_t OT = (uint32_t)TILE_ROUNDS * BLK;
-  constexpr int OWPB = BLK / WAVE;
+  constexpr uint32_t OT = OS_TILE;
+  constexpr int OWPB = OS_BLOCK / WAVE;
   constexpr int RW = OWPB * TILE_ROUNDS;
   constexpr size_t CNT_BYTES = (size_t)RW * RADIX * 2;
   constexpr size_t KEY_BYTES = (size_t)OT * sizeof(KeyT);
   constexpr size_t UNION_BYTES = CNT_BYTES > KEY_BYTES ? CNT_BYTES : KEY_BYTES;
   __shared__ __attribute__((aligned(16))) uint8_t u_raw[UNION_BYTES];
   __shared__ uint32_t ls_a0[OT];
-  __shared__ uint32_t ls_a1[HAS_A1 ? OT : 1];
-  __shared__ uint64_t ls_b64[HAS_B64 ? OT : 1];
   __shared__ uint32_t tileoff[RADIX];
   __shared__ uint32_t excl[RADIX];
   __shared__ uint32_t s_tile;
@@ -774,23 +739,19 @@ __global__ __launch_bounds__(BLK) void k_onesweep_pass(
   const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   KeyT my_key[TILE_ROUNDS];
   uint32_t my_a0[TILE_ROUNDS];
-  uint32_t my_a1v[HAS_A1 ? TILE_ROUNDS : 1];
-  uint64_t my_b64[HAS_B64 ? TILE_ROUNDS : 1];
   uint16_t my_rank[TILE_ROUNDS];
   uint16_t my_dig[TILE_ROUNDS];
   /* load phase first: every round's gathers issue back-to-back so the
      memory latency is paid once per tile, not once per ranking round */
   #pragma unroll
   for (int r = 0; r < TILE_ROUNDS; r++) {
-    uint32_t i = start + (uint32_t)r * BLK + threadIdx.x;
+    uint32_t i = start + (uint32_t)r * OS_BLOCK + threadIdx.x;
     bool active = i < end;
     my_key[r] = active ? keys_in[i] : (KeyT)0;
     my_a0[r] = active ? a0_in[i] : 0;
-    if (HAS_A1) my_a1v[r] = active ? a1_in[i] : 0;
-    if (HAS_B64) my_b64[r] = active ? b64_in[i] : 0;
   }
   for (int r = 0; r < TILE_ROUNDS; r++) {
-    uint32_t i = start + (uint32_t)r * BLK + threadIdx.x;
+    uint32_t i = start + (uint32_t)r * OS_BLOCK + threadIdx.x;
     bool active = i < end;
     uint32_t d = active ? ((uint32_t)(my_key[r] >> (8 * byte_idx)) & 0xFF) : 0u;
     uint64_t m = ~0ull;
@@ -850,13 +811,11 @@ __global__ __launch_bounds__(BLK) void k_onesweep_pass(
   }
   __syncthreads(); /* cnt consumed; region becomes the key staging */
   for (int r = 0; r < TILE_ROUNDS; r++) {
-    uint32_t i = start + (uint32_t)r * BLK + threadIdx.x;
+    uint32_t i = start + (uint32_t)r * OS_BLOCK + threadIdx.x;
     if (i < end) {
       uint32_t slot = my_slot[r];
       ls_key[slot] = my_key[r];
       ls_a0[slot] = my_a0[r];
-      if (HAS_A1) ls_a1[slot] = my_a1v[r];
-      if (HAS_B64) ls_b64[slot] = my_b64[r];
     }
   }
   /* lookback overlapped after placement */
@@ -888,8 +847,6 @@ __global__ __launch_bounds__(BLK) void k_onesweep_pass(
     uint32_t pos = bases[d] + excl[d] + (j - tileoff[d]);
     keys_out[pos] = k;
     a0_out[pos] = ls_a0[j];
-    if (HAS_A1) a1_out[pos] = ls_a1[j];
-    if (HAS_B64) b64_out[pos] = ls_b64[j];
   }
 }
 
@@ -1011,32 +968,15 @@ __global__ __launch_bounds__(BLOCK) void k_scan_lookback(
 }
 
 /* ---- refinement ---- */
-/* eq[i] = 1 if sorted element i has same (still-ambiguous) key prefix as i-1 */
-__global__ void k_eq_init2(const uint64_t* skeys, const uint64_t* lo,
-                           uint8_t* eq, int pbits, uint32_t* parts,
-                           uint32_t n) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    uint64_t k = skeys[i];
-    eq[i] = (i > 0 && k == skeys[i - 1] && lo[i] == lo[i - 1]) ? 1 : 0;
-    parts[i] = pbits ? (uint32_t)(k >> (64 - pbits)) : 0;
-  }
-}
-__global__ void k_eq_init(const uint64_t* skeys, uint8_t* eq, int pbits,
-                          uint32_t* parts, uint32_t n) {
-  /* also materializes the per-position partition ids (composite top bits) —
-     skey positions are stable under refinement (intra-run permutations swap
-     EQUAL composites), so this single read serves both */
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    uint64_t k = skeys[i];
-    eq[i] = (i > 0 && k == skeys[i - 1]) ? 1 : 0;
-    parts[i] = pbits ? (uint32_t)(k >> (64 - pbits)) : 0;
-  }
-}
 /* One pass over the sorted composites for everything the host and the
- * refinement need before the first level: eq + parts exactly as
- * k_eq_init/k_eq_init2 write them (lo == NULL: composites only), plus
+ * refinement need before the first level:
+ *   eq[i]           = 1 if sorted element i has the same (still-ambiguous)
+ *                     key prefix as i-1: equal composites, and equal lo keys
+ *                     where the merged entry path passes them (lo != NULL)
+ *   parts[i]        = partition id of position i (composite top bits).
+ *                     Positions are stable under refinement (intra-run
+ *                     permutations swap EQUAL composites), so this single
+ *                     read of the composites serves both.
  *   meta[0]        += number of set eq flags (one atomic per block)
  *   meta[1 + q]     = first sorted position of partition q, q in [0, P];
  *                     meta[1 + P] = n.  No atomics: in sorted order the
@@ -1145,17 +1085,6 @@ __global__ __launch_bounds__(BLOCK) void k_post_sort_meta(
     tile_inrun[tile] = tot >> 16;
   }
 }
-/* inrun[i] = eq[i] || eq[i+1]; runstart[i] = inrun && !eq[i].
- * Both 0/1 flags ride ONE u64 as (inrun << 32) | runstart so a single
- * scan_u64 produces both prefix sums — each field's total is <= n <= 2^32-1
- * so the low field can never carry into the high one. */
-__global__ void k_run_flags(const uint8_t* eq, uint64_t* packed, uint32_t n) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    uint64_t in = (eq[i] || (i + 1 < n && eq[i + 1])) ? 1 : 0;
-    packed[i] = (in << 32) | (uint64_t)(in && !eq[i]);
-  }
-}
 /* level keys for EVERY record in original-record order (coalesced off/klen/
  * data reads): used when most elements are still ambiguous — a random
  * per-element gather through sidx is latency-bound, the dense build + one
@@ -1180,50 +1109,6 @@ __global__ void k_build_lkeys(RecTable rt, int level_byte0, int use_len_level,
     lk0[g] = k;
   }
 }
-/* compact ambiguous elements; seg = run rank; gather level key (from lk0
- * when prebuilt, else straight from the record table) */
-__global__ void k_compact_refine(RecTable rt, const uint32_t* sidx,
-                                 const uint8_t* eq,
-                                 const uint64_t* packed_scan,
-                                 uint32_t n, int level_byte0, int use_len_level,
-                                 int ser_mode, const uint64_t* lk0,
-                                 uint64_t* lkey, uint32_t* seg, uint32_t* pos) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    uint8_t in = eq[i] || (i + 1 < n && eq[i + 1]);
-    if (!in) continue;
-    uint64_t ps = packed_scan[i];
-    uint32_t j = (uint32_t)(ps >> 32);
-    /* run rank via the EXCLUSIVE runstart scan: rank = scan + is_start - 1 */
-    uint32_t is_start = (eq[i] == 0) ? 1u : 0u;
-    uint32_t sg = (uint32_t)(ps & 0xFFFFFFFFu) + is_start - 1;
-    uint64_t k = 0;
-    if (lk0) {
-      k = lk0[sidx[i]];
-    } else if (use_len_level) {
-      RecView v = rt_view(rt, sidx[i]);
-      k = ser_mode ? v.klen : v.clen;
-    } else {
-      RecView v = rt_view(rt, sidx[i]);
-      const uint8_t* src = ser_mode ? v.key : v.content;
-      uint32_t slen = ser_mode ? v.klen : v.clen;
-      for (int b = 0; b < 8; b++) {
-        uint32_t cb = (uint32_t)(level_byte0 + b);
-        uint8_t byte = (cb < slen) ? src[cb] : 0;
-        k |= (uint64_t)byte << (56 - 8 * b);
-      }
-    }
-    lkey[j] = k;
-    seg[j] = sg;
-    pos[j] = i;
-  }
-}
-/* fused run-flags + decoupled-lookback scan + compaction: one kernel
- * replaces k_run_flags + scan_u64 + k_compact_refine (the separate chain
- * wrote and re-read an 8n flag array and re-read eq — ~24 B/element of
- * scratch traffic; C3's refinement was the dominant profile block).
- * Packed u64 counters: (inrun << 32) | runstart, same protocol as
- * k_scan_lookback. */
 /* One thread publishes its tile's aggregate and resolves the tile's
  * exclusive prefix by look-back (tile 0: inclusive at once).  Every tile
  * that took a ticket must come through here exactly once, whether it has
@@ -1253,7 +1138,18 @@ __device__ __forceinline__ uint64_t d_oss_publish_lookback(
                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return e;
 }
-/* tile_inrun (nullable): per-tile in-run counts from k_post_sort_meta at
+/* One refinement level's compaction in one kernel: run flags, a
+ * decoupled-lookback scan over them and the compaction itself.
+ *   inrun[i] = eq[i] || eq[i+1];  runstart[i] = inrun[i] && !eq[i]
+ * Both 0/1 flags ride ONE u64 as (inrun << 32) | runstart (same protocol as
+ * k_scan_lookback), so one scan yields both prefix sums; each field's total
+ * is <= n <= 2^32-1, so the low field never carries into the high one.
+ * In-run element i lands at j = scan.inrun with seg = its run's rank
+ * (scan.runstart + is_start - 1), pos = i and its level key, read from lk0
+ * when prebuilt and straight from the record table otherwise.  A flag array
+ * written, scanned and re-read by separate kernels cost ~24 B/element of
+ * scratch traffic (C3's refinement was the dominant profile block).
+ * tile_inrun (nullable): per-tile in-run counts from k_post_sort_meta at
  * level 0.  eq flags are only ever cleared after that (k_eq_update), so a
  * zero there stays a proof that the tile has nothing to compact at every
  * later level: such a tile publishes a zero aggregate and returns without
@@ -1401,14 +1297,6 @@ __global__ void k_refine_scatter(const uint32_t* slot_positions, const uint32_t*
        j += gridDim.x * blockDim.x)
     sidx[slot_positions[j]] = tmp[j];
 }
-__global__ void k_refine_apply(const uint32_t* pos_sorted_elements /* pos[j] after sort */,
-                               const uint32_t* slot_positions /* ascending positions */,
-                               const uint32_t* old_sidx, uint32_t* new_sidx,
-                               uint32_t m) {
-  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m;
-       j += gridDim.x * blockDim.x)
-    new_sidx[slot_positions[j]] = old_sidx[pos_sorted_elements[j]];
-}
 /* update eq inside runs after a refine level; counts survivors so the next
  * level can skip its full-n ambiguity pass */
 __global__ void k_eq_update(const uint64_t* lkey_sorted, const uint32_t* seg_sorted,
@@ -1515,24 +1403,7 @@ __global__ void k_iota(uint32_t* a, uint32_t n) {
  * merged run order for equal composites is (segment, in-segment position) =
  * global-id order — exactly the stable union re-sort's order, which keeps
  * the refinement stage's output bit-identical. */
-#define MP_IPT 16
 #define MP_BLOCK 256
-#define MP_TILE (MP_IPT * MP_BLOCK)
-
-/* diagonal split: # taken from A at output rank D (A wins ties) */
-__device__ __forceinline__ uint32_t d_mp_diag(
-    const uint64_t* ka, uint64_t maskA, uint32_t na,
-    const uint64_t* kb, uint64_t maskB, uint32_t nb, uint64_t D) {
-  uint32_t lo = (D > nb) ? (uint32_t)(D - nb) : 0;
-  uint32_t hi = (D < na) ? (uint32_t)D : na;
-  while (lo < hi) {
-    uint32_t mid = lo + ((hi - lo) >> 1);
-    if ((ka[mid] & maskA) <= (kb[D - 1 - mid] & maskB)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 /* nondecreasing check over composites (validates add_sorted_segment input) */
 __global__ void k_check_sorted(const uint64_t* k, uint32_t n, uint32_t* bad) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -1749,13 +1620,14 @@ __global__ void k_writer_same(RecTable rt, const uint32_t* sidx, const uint8_t* 
  * IFile.java:444-615): batch of 64 records per wave iteration — each lane
  * fetches ONE record's descriptor in parallel, then two records are kept in
  * flight per wave (independent 32-lane halves + a 2-deep rotate pipeline)
- * so gather latency overlaps stores.  Records longer than 128 B take the
+ * so gather latency overlaps stores.  A wave with a record longer than
+ * 128 B or a header longer than 8 B, and the partial last wave, take the
  * simple per-record loop. */
 __global__ void k_emit_records(const RecDesc* desc, const uint8_t* same,
                                   const uint64_t* scan, const uint32_t* parts,
                                   const uint64_t* seg_payload_start,
                                   const uint64_t* part_scan_base,
-                                  uint8_t* out, uint32_t n, int force_simple) {
+                                  uint8_t* out, uint32_t n) {
   constexpr int HB = 4; /* bytes per lane per record (records to 128 B) */
   uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -1797,8 +1669,7 @@ __global__ void k_emit_records(const RecDesc* desc, const uint8_t* same,
       if (v2 > maxlen) maxlen = v2;
     }
     uint64_t hdr_ok = __ballot(my_hdr <= 8);
-    if (nvalid == WAVE && maxlen <= 32 * HB && hdr_ok == ~0ull &&
-        !force_simple) {
+    if (nvalid == WAVE && maxlen <= 32 * HB && hdr_ok == ~0ull) {
       /* half h handles records 2r+h; 2-deep rotate pipeline per half.
        * Byte-granular moves are the measured optimum here: a word-funnel
        * STORE variant ran 17.7 vs 10.3 ms (register pressure), and a
@@ -1860,232 +1731,6 @@ __global__ void k_emit_records(const RecDesc* desc, const uint8_t* same,
         w += hdr;
         const uint8_t* sp = (const uint8_t*)(uintptr_t)src;
         for (uint32_t b = lane; b < len; b += WAVE) w[b] = sp[b];
-      }
-    }
-  }
-}
-
-/* Staged-gather emit v2: each wave takes 64 records; every lane issues ALL
- * of its own record's dword loads at once (64 records x ~23 loads of MLP —
- * the rotate pipeline kept only 2 records in flight and sat 70% parked,
- * PMC r2), staging the raw source words into LDS; the drain then runs the
- * proven byte-store path against LDS instead of global.  Records longer
- * than EMIT2_CAP bytes fall back to the per-record global loop. */
-#define EMIT2_CAP 128
-#define EMIT2_W (EMIT2_CAP / 4 + 2)
-__global__ __launch_bounds__(BLOCK) void k_emit_records_v2(
-    const RecDesc* desc, const uint8_t* same, const uint64_t* scan,
-    const uint32_t* parts, const uint64_t* seg_payload_start,
-    const uint64_t* part_scan_base, uint8_t* out, uint32_t n) {
-  __shared__ uint32_t stage[WPB][WAVE][EMIT2_W];
-  uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  uint32_t lane = threadIdx.x & (WAVE - 1);
-  uint32_t wv = threadIdx.x / WAVE;
-  uint32_t nwaves = (gridDim.x * blockDim.x) / WAVE;
-  for (uint64_t base = (uint64_t)wave * WAVE; base < n;
-       base += (uint64_t)nwaves * WAVE) {
-    uint32_t i = (uint32_t)base + lane;
-    uint64_t my_src = 0, my_dst = 0, my_h0 = 0, my_h1 = 0;
-    uint32_t my_len = 0, my_hdr = 0, my_ph = 0;
-    if (i < n) {
-      RecDesc v = desc[i];
-      uint32_t p = parts[i];
-      my_dst = seg_payload_start[p] + (scan[i] - part_scan_base[p]);
-      uint8_t prev_same = (i > 0 && parts[i] == parts[i - 1]) ? same[i - 1] : 0;
-      uint8_t hdrbuf[16] = {0};
-      uint32_t hdr = 0;
-      if (same[i]) {
-        if (!prev_same) hdrbuf[hdr++] = 0xFE;
-        hdr += d_vint_write(hdrbuf + hdr, v.vlen);
-        my_src = v.src + v.klen;
-        my_len = v.vlen;
-      } else {
-        if (prev_same) hdrbuf[hdr++] = 0xFD;
-        hdr += d_vint_write(hdrbuf + hdr, v.klen);
-        hdr += d_vint_write(hdrbuf + hdr, v.vlen);
-        my_src = v.src;
-        my_len = v.klen + v.vlen;
-      }
-      my_hdr = hdr;
-      for (int b = 0; b < 8; b++) my_h0 |= (uint64_t)hdrbuf[b] << (8 * b);
-      for (int b = 8; b < 12; b++) my_h1 |= (uint64_t)hdrbuf[b] << (8 * (b - 8));
-    }
-    uint32_t nvalid = (n - base < WAVE) ? (uint32_t)(n - base) : WAVE;
-    uint32_t maxlen = my_len;
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-      uint32_t v2 = __shfl_xor(maxlen, sh);
-      if (v2 > maxlen) maxlen = v2;
-    }
-    if (maxlen <= EMIT2_CAP) {
-      /* stage: aligned dword loads from src&~3 — ALL records in flight */
-      my_ph = (uint32_t)(my_src & 3);
-      const uint32_t* sw = (const uint32_t*)(my_src & ~3ull);
-      uint32_t nw = (my_ph + my_len + 3) >> 2;
-      uint32_t* row = stage[wv][lane];
-      #pragma unroll 4
-      for (uint32_t k = 0; k < nw; k++) row[k] = sw[k];
-      /* drain: per record, whole wave cooperates; source = LDS */
-      for (uint32_t r = 0; r < nvalid; r++) {
-        uint64_t dsto = __shfl(my_dst, r);
-        uint64_t h0 = __shfl(my_h0, r);
-        uint64_t h1 = __shfl(my_h1, r);
-        uint32_t len = __shfl(my_len, r);
-        uint32_t hdr = __shfl(my_hdr, r);
-        uint32_t ph = __shfl(my_ph, r);
-        uint8_t* w = out + dsto;
-        if (lane < hdr)
-          w[lane] = (lane < 8) ? (uint8_t)(h0 >> (8 * lane))
-                               : (uint8_t)(h1 >> (8 * (lane - 8)));
-        w += hdr;
-        const uint8_t* ls = (const uint8_t*)stage[wv][r] + ph;
-        for (uint32_t b = lane; b < len; b += WAVE) w[b] = ls[b];
-      }
-    } else {
-      for (uint32_t r = 0; r < nvalid; r++) {
-        uint64_t src = __shfl(my_src, r);
-        uint64_t dsto = __shfl(my_dst, r);
-        uint64_t h0 = __shfl(my_h0, r);
-        uint64_t h1 = __shfl(my_h1, r);
-        uint32_t len = __shfl(my_len, r);
-        uint32_t hdr = __shfl(my_hdr, r);
-        uint8_t* w = out + dsto;
-        if (lane < hdr)
-          w[lane] = (lane < 8) ? (uint8_t)(h0 >> (8 * lane))
-                               : (uint8_t)(h1 >> (8 * (lane - 8)));
-        w += hdr;
-        const uint8_t* sp2 = (const uint8_t*)(uintptr_t)src;
-        for (uint32_t b = lane; b < len; b += WAVE) w[b] = sp2[b];
-      }
-    }
-  }
-}
-
-/* Staged-span emit: each WAVE owns 64 consecutive sorted records — within a
- * partition their output bytes are one contiguous span.  Every lane stages
- * its own record (header regs + funneled u32 window loads) into a wave-local
- * LDS image laid out so image words map to 4-aligned OUTPUT words, then the
- * wave stores the span as dense aligned u32s.  Wave-synchronous (no
- * barriers); LDS byte writes are byte-granular so record boundaries need no
- * read-modify-write.  Cross-partition / short / oversized waves fall back to
- * the per-record loop.  Fixes the two measured failure modes: scattered
- * partial-line stores (lane-per-record v1) and per-rotate register pressure
- * (word-funnel v2), while keeping 64 records of gather MLP in flight. */
-#define SPAN_BYTES (64 * 144 + 16)
-__global__ __launch_bounds__(BLOCK) void k_emit_span(
-    const RecDesc* desc, const uint8_t* same, const uint64_t* scan,
-    const uint32_t* parts, const uint64_t* seg_payload_start,
-    const uint64_t* part_scan_base, uint8_t* out, uint32_t n) {
-  __shared__ __attribute__((aligned(16))) uint8_t img8[WPB][SPAN_BYTES];
-  uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  uint32_t lane = threadIdx.x & (WAVE - 1);
-  uint32_t wv = threadIdx.x / WAVE;
-  uint32_t nwaves = (gridDim.x * blockDim.x) / WAVE;
-  uint8_t* img = img8[wv];
-  uint32_t* img32 = (uint32_t*)img;
-  for (uint64_t base = (uint64_t)wave * WAVE; base < n;
-       base += (uint64_t)nwaves * WAVE) {
-    uint32_t i = (uint32_t)base + lane;
-    uint64_t my_src = 0, my_dst = 0, my_h0 = 0, my_h1 = 0;
-    uint32_t my_len = 0, my_hdr = 0, my_p = 0;
-    if (i < n) {
-      RecDesc v = desc[i];
-      my_p = parts[i];
-      my_dst = seg_payload_start[my_p] + (scan[i] - part_scan_base[my_p]);
-      uint8_t prev_same = (i > 0 && parts[i] == parts[i - 1]) ? same[i - 1] : 0;
-      uint8_t hdrbuf[16] = {0};
-      uint32_t hdr = 0;
-      if (same[i]) {
-        if (!prev_same) hdrbuf[hdr++] = 0xFE;
-        hdr += d_vint_write(hdrbuf + hdr, v.vlen);
-        my_src = v.src + v.klen;
-        my_len = v.vlen;
-      } else {
-        if (prev_same) hdrbuf[hdr++] = 0xFD;
-        hdr += d_vint_write(hdrbuf + hdr, v.klen);
-        hdr += d_vint_write(hdrbuf + hdr, v.vlen);
-        my_src = v.src;
-        my_len = v.klen + v.vlen;
-      }
-      my_hdr = hdr;
-      for (int b = 0; b < 8; b++) my_h0 |= (uint64_t)hdrbuf[b] << (8 * b);
-      for (int b = 8; b < 12; b++) my_h1 |= (uint64_t)hdrbuf[b] << (8 * (b - 8));
-    }
-    uint32_t nvalid = (n - base < WAVE) ? (uint32_t)(n - base) : WAVE;
-    uint32_t p0 = __shfl(my_p, 0);
-    uint64_t okb = __ballot(i >= n || my_p == p0);
-    uint64_t span0 = __shfl(my_dst, 0);
-    uint64_t span_end = __shfl(my_dst + my_hdr + my_len, WAVE - 1);
-    uint32_t s = (uint32_t)(span0 & 3);
-    uint64_t span_len = span_end - span0;
-    if (nvalid == WAVE && okb == ~0ull && s + span_len <= SPAN_BYTES - 8) {
-      uint32_t io = (uint32_t)(my_dst - span0) + s;
-      uint32_t tot = my_hdr + my_len;
-      const uint8_t* sp = (const uint8_t*)(uintptr_t)my_src;
-      /* A: bytes up to the first aligned word boundary past the header */
-      uint32_t B0 = (io + my_hdr + 3) & ~3u;
-      if (B0 > io + tot) B0 = io + tot;
-      for (uint32_t q = io; q < B0; q++) {
-        uint32_t k = q - io;
-        img[q] = (k < my_hdr) ? ((k < 8) ? (uint8_t)(my_h0 >> (8 * k))
-                                         : (uint8_t)(my_h1 >> (8 * (k - 8))))
-                              : sp[k - my_hdr];
-      }
-      /* B: full image words from funneled source window words, in batches of
-         8 so the global loads issue independently (a serial prev/next funnel
-         chain measured 3x slower: one vmcnt stall per word) */
-      uint32_t B1 = (io + tot) & ~3u;
-      if (B1 > B0) {
-        uint32_t off0 = B0 - io - my_hdr;
-        uint64_t S = my_src + off0;
-        const uint32_t* sw = (const uint32_t*)(S & ~3ull);
-        uint32_t sh = (uint32_t)(S & 3), nw = (B1 - B0) >> 2;
-        uint32_t jw = B0 >> 2;
-        uint32_t j = 0;
-        while (j < nw) {
-          uint32_t cnt = nw - j;
-          if (cnt > 8) cnt = 8;
-          uint32_t r[9];
-          #pragma unroll
-          for (uint32_t k = 0; k < 9; k++)
-            if (k <= cnt) r[k] = sw[j + k];
-          #pragma unroll
-          for (uint32_t k = 0; k < 8; k++)
-            if (k < cnt)
-              img32[jw + j + k] =
-                  sh ? ((r[k] >> (8 * sh)) | (r[k + 1] << (8 * (4 - sh)))) : r[k];
-          j += cnt;
-        }
-      }
-      /* C: tail bytes */
-      for (uint32_t q = (B1 > B0 ? B1 : B0); q < io + tot; q++)
-        img[q] = sp[q - io - my_hdr];
-      /* wave store: head bytes, dense aligned words, tail bytes */
-      uint32_t hb = (4 - s) & 3;
-      if (hb > span_len) hb = (uint32_t)span_len;
-      if (lane < hb) out[span0 + lane] = img[s + lane];
-      uint32_t j0 = (s + hb) >> 2;
-      uint32_t j1 = (uint32_t)((s + span_len) >> 2);
-      for (uint32_t j = j0 + lane; j < j1; j += WAVE)
-        *(uint32_t*)(out + span0 - s + 4ull * j) = img32[j];
-      uint32_t tpos = 4u * j1;
-      uint32_t tend = (uint32_t)(s + span_len);
-      if (lane < tend - tpos) out[span0 - s + tpos + lane] = img[tpos + lane];
-    } else {
-      /* fallback: one record at a time, whole wave cooperates */
-      for (uint32_t r = 0; r < nvalid; r++) {
-        uint64_t src = __shfl(my_src, r);
-        uint64_t dsto = __shfl(my_dst, r);
-        uint64_t h0 = __shfl(my_h0, r);
-        uint64_t h1 = __shfl(my_h1, r);
-        uint32_t len = __shfl(my_len, r);
-        uint32_t hdr = __shfl(my_hdr, r);
-        uint8_t* w = out + dsto;
-        if (lane < hdr)
-          w[lane] = (lane < 8) ? (uint8_t)(h0 >> (8 * lane))
-                               : (uint8_t)(h1 >> (8 * (lane - 8)));
-        w += hdr;
-        const uint8_t* sp2 = (const uint8_t*)(uintptr_t)src;
-        for (uint32_t b = lane; b < len; b += WAVE) w[b] = sp2[b];
       }
     }
   }
@@ -2160,54 +1805,6 @@ __global__ __launch_bounds__(BLOCK) void k_emit_uniform_arith(
         const uint8_t* sp2 = (const uint8_t*)(uintptr_t)src;
         for (uint32_t b = lane; b < rec_u; b += WAVE) w[b] = sp2[b];
       }
-    }
-  }
-}
-
-/* Uniform-record emit fast path: when every record serializes to the same
- * length and RLE is off, the IFile body is a constant-stride stream
- * (hdr vints ‖ key ‖ val per record).  One LANE per record: the 88-byte
- * C2 record moves as eleven u64 loads and ~12 u64 stores (head/tail bytes
- * for output alignment) instead of the generic path's byte-granular
- * half-wave gather — ~20x fewer issue slots, dense aggregate writes. */
-template <typename WordT, int MAXW>
-__global__ __launch_bounds__(BLOCK) void k_emit_uniform(
-    const RecDesc* desc, const uint64_t* scan, const uint32_t* parts,
-    const uint64_t* seg_payload_start, const uint64_t* part_scan_base,
-    uint8_t* out, uint32_t n, uint32_t hdrlen /* <= 8 */, uint64_t hdrword,
-    uint32_t reclen /* = klen+vlen; % sizeof(WordT) == 0; <= MAXW words */) {
-  constexpr uint32_t WB = (uint32_t)sizeof(WordT);
-  const uint32_t total = hdrlen + reclen;
-  const uint32_t nwords = reclen / WB;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    uint32_t p = parts[i];
-    uint64_t dst = seg_payload_start[p] + (scan[i] - part_scan_base[p]);
-    const WordT* srcw = (const WordT*)(uintptr_t)desc[i].src;
-    WordT s[MAXW + 1];
-    #pragma unroll
-    for (uint32_t k = 0; k < MAXW + 1; k++) s[k] = (k < nwords) ? srcw[k] : 0;
-    /* q0: first logical offset >= hdrlen that is WB-aligned in OUTPUT */
-    uint32_t a = (uint32_t)(dst % WB);
-    uint32_t q0 = hdrlen + ((WB - ((a + hdrlen) % WB)) % WB);
-    for (uint32_t q = 0; q < q0 && q < total; q++) {
-      uint8_t b = (q < hdrlen) ? (uint8_t)(hdrword >> (8 * q))
-                               : (uint8_t)(s[0] >> (8 * (q - hdrlen)));
-      out[dst + q] = b;
-    }
-    /* aligned word body: word k covers logical [q0 + WB*k, +WB) */
-    uint32_t c = (q0 - hdrlen) % WB;
-    uint32_t kmax = (total >= q0 + WB) ? (total - q0) / WB : 0;
-    WordT* ww = (WordT*)(out + dst + q0);
-    if (c == 0) {
-      for (uint32_t k = 0; k < kmax; k++) ww[k] = s[k];
-    } else {
-      for (uint32_t k = 0; k < kmax; k++)
-        ww[k] = (WordT)((s[k] >> (8 * c)) | (s[k + 1] << (8 * (WB - c))));
-    }
-    for (uint32_t q = q0 + WB * kmax; q < total; q++) {
-      uint32_t o = q - hdrlen;
-      out[dst + q] = (uint8_t)(s[o / WB] >> (8 * (o % WB)));
     }
   }
 }
@@ -3625,13 +3222,57 @@ struct DBuf {
   void release() { if (p) { pool_free(p, sz); p = nullptr; sz = 0; } }
 };
 
+/* The environment switches (table in DESIGN.md).  Each forces a fallback
+ * that other inputs take anyway, so a test can reach it at a small size.
+ * ENV_SET matches a variable that is set at all, ENV_ZERO one whose value
+ * starts with '0'.  With `cache` (a static int at the call site, -1 at
+ * first) the first answer holds for the life of the process; without it the
+ * variable is read on every call, so a test can flip it in-process. */
+enum EnvTest { ENV_SET, ENV_ZERO };
+static bool env_switch(const char* name, EnvTest t, int* cache = nullptr) {
+  if (cache && *cache >= 0) return *cache != 0;
+  const char* e = getenv(name);
+  bool on = (t == ENV_SET) ? e != nullptr : (e && e[0] == '0');
+  if (cache) *cache = on ? 1 : 0;
+  return on;
+}
+
+/* Gate of k_build_composite_stream: one contiguous, 16-byte aligned buffer
+ * of uniform BYTES-key records of rec_u/4 <= 32 whole dwords.
+ * TZS_STREAM_UNIFORM=0 selects k_build_composite2 instead. */
+static bool stream_uniform_gate(const RecTable& rt) {
+  if (env_switch("TZS_STREAM_UNIFORM", ENV_ZERO)) return false;
+  return rt.nspills == 1 && rt.key_type == 0 && rt.rec_u0 != 0 &&
+         rt.klen_u0 >= 4 && rt.klen_u0 <= rt.rec_u0 && rt.rec_u0 % 4 == 0 &&
+         rt.rec_u0 <= 128 && ((uintptr_t)rt.data0 & 15) == 0;
+}
+
+/* hipEvent_t set destroyed on every return path.  Events are created on
+ * demand, in index order. */
+template <int N>
+struct Events {
+  hipEvent_t ev[N];
+  int made = 0;
+  Events() = default;
+  Events(const Events&) = delete;
+  Events& operator=(const Events&) = delete;
+  ~Events() { for (int i = 0; i < made; i++) (void)hipEventDestroy(ev[i]); }
+  void create(int upto) { while (made < upto && made < N) (void)hipEventCreate(&ev[made++]); }
+  void record(int i) { (void)hipEventRecord(ev[i]); }
+  int64_t ns(int a, int b) const {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev[a], ev[b]);
+    return (int64_t)(ms * 1e6);
+  }
+};
+
 /* exclusive scan of u64 array (device), returns total via last+add trick */
 static int scan_u64(const uint64_t* d_in, uint64_t* d_out, uint32_t n, uint64_t* h_total) {
   if (n == 0) { if (h_total) *h_total = 0; return 0; }
   {
     /* single-pass decoupled-lookback path (one read + one write) */
-    static int no_oss = -1;
-    if (no_oss < 0) no_oss = getenv("TZS_NO_SCAN_LOOKBACK") ? 1 : 0;
+    static int no_oss_c = -1;
+    const bool no_oss = env_switch("TZS_NO_SCAN_LOOKBACK", ENV_SET, &no_oss_c);
     uint32_t nb_l = nblocks_for(n, SCAN_TILE);
     if (!no_oss && nb_l > 8) {
       static thread_local DBuf st, tick;
@@ -3779,7 +3420,7 @@ static int radix_sort(KeyT* d_key, uint32_t* d_a0, uint32_t* d_a1, uint32_t n,
   DBuf& tb64 = g_rs_tb64;
   if (has_b64 && tb64.alloc(sizeof(uint64_t) * n)) return -12;
 
-  hipEvent_t evs[16], eve[16];
+  Events<32> ev; /* scatter pass p: start = ev[2p], end = ev[2p+1] */
   int nev = 0;
   KeyT* kin = d_key;
   KeyT* kout = (KeyT*)tk.p;
@@ -3792,53 +3433,21 @@ static int radix_sort(KeyT* d_key, uint32_t* d_a0, uint32_t* d_a1, uint32_t n,
   int passes = 0;
   bool pass_skip[16] = {false};
 
-  /* onesweep path (any key width / payload shape, incl. the refinement
-     seg-sorts): one global-histogram read for all passes, then a single
-     lookback kernel per pass.  Falls back to the classic 3-kernel pass on a
-     lookback timeout. */
-  static int use_onesweep = -1;
-  if (use_onesweep < 0) {
-    const char* e = getenv("TZS_ONESWEEP");
-    use_onesweep = (e && e[0] == '0') ? 0 : 1;
-  }
-  /* payload-carrying onesweep (a1/b64 staged through LDS) measured SLOWER
-     than the classic 3-kernel path on C3's refinement seg-sorts (48.9 ->
-     44.9 GB/s): the 50-57 KB LDS footprint halves resident blocks and each
-     seg-sort pays a host histogram sync.  The dispatch below supports every
-     shape; the gate keeps onesweep to the base (key + record-id) sort where
-     it wins. */
-  /* payload shapes ride onesweep too since the barrier-light rewrite:
-     u64+two-u32 payloads at 1024 threads (130 KB LDS, 16 waves/CU);
-     u32-key+u64 payload at 256 (41 KB, 12 waves/CU — the 1024 variant
-     would need 162 KB).  Pre-rewrite this measured slower and was gated
-     off. */
-  /* payload shapes (the refinement's level-key and run-id sorts) can ride
-     onesweep at 256-thread tiles (the 1024 a1 instantiation exceeds LDS at
-     12 rounds); re-testable now that the histogram prefix is device-side
-     (TZS_OS_PAYLOAD=1) */
-  static int os_payload = -1;
-  if (os_payload < 0) {
-    const char* e = getenv("TZS_OS_PAYLOAD");
-    os_payload = (e && e[0] == '1') ? 1 : 0;
-  }
-  bool os_shape_ok = (!has_a1 && !has_b64) ||
-                     (os_payload && !(has_a1 && has_b64));
-  if (use_onesweep && os_shape_ok && n >= 20000) {
+  /* onesweep path: one global-histogram read for all passes, then a single
+     lookback kernel per pass.  It takes the base sort's shape only (key +
+     record id, no a1/b64 payload).  The refinement's payload-carrying
+     seg-sorts stay on the classic 3-kernel pass: staging a1/b64 through LDS
+     at 256-thread tiles measured slower there (48.9 -> 44.9 GB/s on C3;
+     the 50-57 KB LDS footprint halves resident blocks), and the 1024-thread
+     tile does not fit the LDS with a payload.  Among 256/512/1024-thread
+     tiles the no-payload shape measured 289/293/301 GB/s at C2, so only the
+     1024 one exists.  TZS_ONESWEEP=0 forces the classic
+     pass, which inputs below 20000 elements take anyway. */
+  static int no_onesweep_c = -1;
+  const bool use_onesweep = !env_switch("TZS_ONESWEEP", ENV_ZERO, &no_onesweep_c);
+  if (use_onesweep && !has_a1 && !has_b64 && n >= 20000) {
     int npasses = nbytes_key - first_byte;
-    /* bigger blocks scale the tile while KEEPING 16 waves/CU: 512 threads =
-       4096-elem tile (2 blocks x 8 waves), 1024 = 8192-elem tile (1 block x
-       16 waves, ~135 KB LDS) — digit runs grow to ~32 x 12 B = 384 B so
-       partial-line scatter waste nearly vanishes (measured 289/293/301 GB/s
-       for 256/512/1024 at C2; TZS_OS_BLK overrides) */
-    static int os_blk = -1;
-    if (os_blk < 0) {
-      const char* e = getenv("TZS_OS_BLK");
-      os_blk = e ? atoi(e) : 1024;
-      if (os_blk != 256 && os_blk != 512 && os_blk != 1024) os_blk = 1024;
-    }
-    int eff_blk = (has_a1 || has_b64) ? 256 : os_blk;
-    uint32_t os_tile = (uint32_t)TILE_ROUNDS * (uint32_t)eff_blk;
-    uint32_t nb_os = nblocks_for(n, os_tile);
+    uint32_t nb_os = nblocks_for(n, OS_TILE);
     static thread_local DBuf gh, gbases, st, tick;
     if (gh.alloc(4u * npasses * RADIX)) return -12;
     if (gbases.alloc(4u * npasses * RADIX)) return -12;
@@ -3857,39 +3466,14 @@ static int radix_sort(KeyT* d_key, uint32_t* d_a0, uint32_t* d_a1, uint32_t n,
       /* reset only the ticket word — the error word ([1]) accumulates across
          passes and is checked once after the loop */
       HIP_CHECK(hipMemsetAsync(tick.p, 0, 4));
-      if (nev < 16) { (void)hipEventCreate(&evs[nev]); (void)hipEventCreate(&eve[nev]);
-                      (void)hipEventRecord(evs[nev]); }
+      if (nev < 16) { ev.create(2 * nev + 2); ev.record(2 * nev); }
       const uint32_t* pbases = (const uint32_t*)((uint32_t*)gbases.p + p * RADIX);
-      if (has_b64) {
-        hipLaunchKernelGGL((k_onesweep_pass<KeyT, false, true, 256>), dim3(nb_os),
-                           dim3(256), 0, 0, kin, kout, a0in, a0out, nullptr,
-                           nullptr, b64in, b64out, n, b, pbases, (uint32_t*)st.p,
-                           (uint32_t*)tick.p, (uint32_t*)tick.p + 1);
-      } else if (has_a1) {
-        hipLaunchKernelGGL((k_onesweep_pass<KeyT, true, false, 256>), dim3(nb_os),
-                           dim3(256), 0, 0, kin, kout, a0in, a0out, a1in, a1out,
-                           nullptr, nullptr, n, b, pbases, (uint32_t*)st.p,
-                           (uint32_t*)tick.p, (uint32_t*)tick.p + 1);
-      } else if (os_blk == 1024)
-        hipLaunchKernelGGL((k_onesweep_pass<KeyT, false, false, 1024>), dim3(nb_os),
-                           dim3(1024), 0, 0, kin, kout, a0in, a0out, nullptr, nullptr,
-                           nullptr, nullptr, n, b, pbases, (uint32_t*)st.p,
-                           (uint32_t*)tick.p, (uint32_t*)tick.p + 1);
-      else if (os_blk == 512)
-        hipLaunchKernelGGL((k_onesweep_pass<KeyT, false, false, 512>), dim3(nb_os),
-                           dim3(512), 0, 0, kin, kout, a0in, a0out, nullptr, nullptr,
-                           nullptr, nullptr, n, b, pbases, (uint32_t*)st.p,
-                           (uint32_t*)tick.p, (uint32_t*)tick.p + 1);
-      else
-        hipLaunchKernelGGL((k_onesweep_pass<KeyT, false, false, 256>), dim3(nb_os),
-                           dim3(256), 0, 0, kin, kout, a0in, a0out, nullptr, nullptr,
-                           nullptr, nullptr, n, b, pbases, (uint32_t*)st.p,
-                           (uint32_t*)tick.p, (uint32_t*)tick.p + 1);
-      if (nev < 16) { (void)hipEventRecord(eve[nev]); nev++; }
+      hipLaunchKernelGGL((k_onesweep_pass<KeyT>), dim3(nb_os), dim3(OS_BLOCK), 0, 0,
+                         kin, kout, a0in, a0out, n, b, pbases, (uint32_t*)st.p,
+                         (uint32_t*)tick.p, (uint32_t*)tick.p + 1);
+      if (nev < 16) { ev.record(2 * nev + 1); nev++; }
       std::swap(kin, kout);
       std::swap(a0in, a0out);
-      if (has_a1) std::swap(a1in, a1out);
-      if (has_b64) std::swap(b64in, b64out);
       passes++;
     }
     {
@@ -3926,98 +3510,44 @@ static int radix_sort(KeyT* d_key, uint32_t* d_a0, uint32_t* d_a1, uint32_t n,
           if (h_cnt2[p * RADIX + d] == n) { pass_skip[p] = true; break; }
     }
   }
-  /* classic path at 512-thread blocks: 4096-element tiles keep 8 waves/CU
-     (1-2 resident blocks) while doubling digit runs; the u64-key + u64-
-     payload variant would exceed the 160 KB LDS at 512 and stays at 256
-     (it is never dispatched at runtime — b64 rides u32 seg keys). */
-  {
-    static int cl_blk = -1;
-    if (cl_blk < 0) {
-      const char* e = getenv("TZS_CL_BLK");
-      cl_blk = e ? atoi(e) : 256;   /* 512 measured neutral on the
-                                        refinement shapes (55.7 vs 56.0
-                                        GB/s C3) — they are bound by the
-                                        compact/gather pattern, not by
-                                        digit-run length */
-      if (cl_blk != 256 && cl_blk != 512) cl_blk = 256;
-    }
-    uint32_t cl_tile = (uint32_t)TILE_ROUNDS * (uint32_t)cl_blk;
-    uint32_t nb_cl = nblocks_for(n, cl_tile);
-    if (nb_cl > nb) nb_cl = nb;  /* counts/offsets were sized for nb */
-    bool use512 = (cl_blk == 512);
-    if (sizeof(KeyT) == 8 && has_b64) use512 = false;  /* LDS > 160 KB */
+  /* 256-thread tiles: 512 measured neutral on the refinement shapes (55.7
+     vs 56.0 GB/s C3) — they are bound by the compact/gather pattern, not by
+     digit-run length */
   for (int b = first_byte; b < nbytes_key; b++) {
     if (b - first_byte < 16 && pass_skip[b - first_byte]) continue;
-    uint32_t nbl = use512 ? nb_cl : nb;
-    if (use512)
-      hipLaunchKernelGGL((k_radix_hist<KeyT, 512>), dim3(nbl), dim3(512), 0, 0,
-                         kin, n, b, (uint32_t*)counts.p);
-    else
-      hipLaunchKernelGGL((k_radix_hist<KeyT>), dim3(nbl), dim3(BLOCK), 0, 0, kin, n, b,
-                         (uint32_t*)counts.p);
+    hipLaunchKernelGGL((k_radix_hist<KeyT>), dim3(nb), dim3(BLOCK), 0, 0, kin, n, b,
+                       (uint32_t*)counts.p);
     hipLaunchKernelGGL(k_radix_scan_blocks, dim3(RADIX), dim3(BLOCK), 0, 0,
-                       (uint32_t*)counts.p, nbl, (uint32_t*)offsets.p, (uint32_t*)totals.p);
+                       (uint32_t*)counts.p, nb, (uint32_t*)offsets.p, (uint32_t*)totals.p);
     hipLaunchKernelGGL(k_radix_scan_digits, dim3(1), dim3(RADIX), 0, 0,
                        (uint32_t*)totals.p, (uint32_t*)bases.p);
-    if (nev < 16) { (void)hipEventCreate(&evs[nev]); (void)hipEventCreate(&eve[nev]);
-                    (void)hipEventRecord(evs[nev]); }
-    if (has_b64) {
-      if constexpr (sizeof(KeyT) == 4) {
-        if (use512) {
-          hipLaunchKernelGGL((k_radix_scatter<KeyT, false, true, 512>), dim3(nbl),
-                             dim3(512), 0, 0, kin, kout, a0in, a0out, nullptr,
-                             nullptr, b64in, b64out, n, b, (uint32_t*)offsets.p,
-                             (uint32_t*)bases.p);
-        } else {
-          hipLaunchKernelGGL((k_radix_scatter<KeyT, false, true>), dim3(nbl),
-                             dim3(BLOCK), 0, 0, kin, kout, a0in, a0out, nullptr,
-                             nullptr, b64in, b64out, n, b, (uint32_t*)offsets.p,
-                             (uint32_t*)bases.p);
-        }
-      } else {
-        hipLaunchKernelGGL((k_radix_scatter<KeyT, false, true>), dim3(nbl),
-                           dim3(BLOCK), 0, 0, kin, kout, a0in, a0out, nullptr,
-                           nullptr, b64in, b64out, n, b, (uint32_t*)offsets.p,
-                           (uint32_t*)bases.p);
-      }
-    } else if (has_a1) {
-      if (use512)
-        hipLaunchKernelGGL((k_radix_scatter<KeyT, true, false, 512>), dim3(nbl),
-                           dim3(512), 0, 0, kin, kout, a0in, a0out, a1in, a1out,
-                           nullptr, nullptr, n, b, (uint32_t*)offsets.p,
-                           (uint32_t*)bases.p);
-      else
-        hipLaunchKernelGGL((k_radix_scatter<KeyT, true>), dim3(nbl), dim3(BLOCK),
-                           0, 0, kin, kout, a0in, a0out, a1in, a1out, nullptr,
-                           nullptr, n, b, (uint32_t*)offsets.p, (uint32_t*)bases.p);
-    } else {
-      if (use512)
-        hipLaunchKernelGGL((k_radix_scatter<KeyT, false, false, 512>), dim3(nbl),
-                           dim3(512), 0, 0, kin, kout, a0in, a0out, nullptr,
-                           nullptr, nullptr, nullptr, n, b, (uint32_t*)offsets.p,
-                           (uint32_t*)bases.p);
-      else
-        hipLaunchKernelGGL((k_radix_scatter<KeyT, false>), dim3(nbl), dim3(BLOCK),
-                           0, 0, kin, kout, a0in, a0out, nullptr, nullptr, nullptr,
-                           nullptr, n, b, (uint32_t*)offsets.p, (uint32_t*)bases.p);
-    }
-    if (nev < 16) { (void)hipEventRecord(eve[nev]); nev++; }
+    if (nev < 16) { ev.create(2 * nev + 2); ev.record(2 * nev); }
+    if (has_b64)
+      hipLaunchKernelGGL((k_radix_scatter<KeyT, false, true>), dim3(nb),
+                         dim3(BLOCK), 0, 0, kin, kout, a0in, a0out, nullptr,
+                         nullptr, b64in, b64out, n, b, (uint32_t*)offsets.p,
+                         (uint32_t*)bases.p);
+    else if (has_a1)
+      hipLaunchKernelGGL((k_radix_scatter<KeyT, true>), dim3(nb), dim3(BLOCK),
+                         0, 0, kin, kout, a0in, a0out, a1in, a1out, nullptr,
+                         nullptr, n, b, (uint32_t*)offsets.p, (uint32_t*)bases.p);
+    else
+      hipLaunchKernelGGL((k_radix_scatter<KeyT, false>), dim3(nb), dim3(BLOCK),
+                         0, 0, kin, kout, a0in, a0out, nullptr, nullptr, nullptr,
+                         nullptr, n, b, (uint32_t*)offsets.p, (uint32_t*)bases.p);
+    if (nev < 16) { ev.record(2 * nev + 1); nev++; }
     std::swap(kin, kout);
     std::swap(a0in, a0out);
     if (has_a1) std::swap(a1in, a1out);
     if (has_b64) std::swap(b64in, b64out);
     passes++;
   }
-  }
 finish:
   (void)hipDeviceSynchronize();
   for (int e = 0; e < nev; e++) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, evs[e], eve[e]);
-    g_scatter_ns += (int64_t)(ms * 1e6);
+    g_scatter_ns += ev.ns(2 * e, 2 * e + 1);
     g_scatter_launches += 1;
     g_scatter_elems += n;
-    (void)hipEventDestroy(evs[e]); (void)hipEventDestroy(eve[e]);
   }
   if (passes & 1) {
     if (dbuf_key && dbuf_a0 && (!has_a1 || dbuf_a1) && (!has_b64 || dbuf_b64)) {
@@ -4262,7 +3792,7 @@ extern "C" int tzs_sorter_write_batch_device(tzs_sorter* s, const void* d_data,
     uint64_t res[4];
     HIP_CHECK(hipMemcpy(res, mm.p, 32, hipMemcpyDeviceToHost));
     bool uni = (res[0] == res[1]) && (res[2] == res[3]) && res[0] <= 0xFFFFFFFFull;
-    if (getenv("TZS_NO_UNIFORM")) uni = false;
+    if (env_switch("TZS_NO_UNIFORM", ENV_SET)) uni = false;
     if (s->cur_first_batch) {
       s->cur_rec_u = uni ? (uint32_t)res[0] : 0;
       s->cur_klen_u = uni ? (uint32_t)res[2] : 0;
@@ -4314,7 +3844,7 @@ extern "C" int tzs_sorter_write_batch_device_adopt(tzs_sorter* s, void* d_data,
   {
     std::lock_guard<std::mutex> lk(pool_mu());
     auto hh = uniform_hints().find(d_off);
-    if (hh != uniform_hints().end() && !getenv("TZS_NO_UNIFORM")) {
+    if (hh != uniform_hints().end() && !env_switch("TZS_NO_UNIFORM", ENV_SET)) {
       s->cur_rec_u = hh->second.rec_u;
       s->cur_klen_u = hh->second.klen_u;
       nbytes = hh->second.nbytes;
@@ -4338,7 +3868,7 @@ extern "C" int tzs_sorter_write_batch_device_adopt(tzs_sorter* s, void* d_data,
     uint64_t res[4];
     HIP_CHECK(hipMemcpy(res, mm.p, 32, hipMemcpyDeviceToHost));
     bool uni = (res[0] == res[1]) && (res[2] == res[3]) && res[0] <= 0xFFFFFFFFull;
-    if (getenv("TZS_NO_UNIFORM")) uni = false;
+    if (env_switch("TZS_NO_UNIFORM", ENV_SET)) uni = false;
     s->cur_rec_u = uni ? (uint32_t)res[0] : 0;
     s->cur_klen_u = uni ? (uint32_t)res[2] : 0;
     s->cur_first_batch = false;
@@ -4432,32 +3962,21 @@ static SortParams derive_sort_params(tzs_sorter* s,
   return sp;
 }
 
-static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
-                           std::vector<uint32_t> hbase,
-                           RecTable rt, uint32_t n, int SB, int ser_mode,
-                           const uint8_t* h_spill_rle, int nspills_rle,
-                           SpillData* outsp, bool apply_combine,
-                           SpillData* retain, const uint64_t* d_lo);
-
-/* Gate of k_build_composite_stream: one contiguous, 16-byte aligned buffer
- * of uniform BYTES-key records of rec_u/4 <= 32 whole dwords.
- * TZS_STREAM_UNIFORM=0 selects k_build_composite2 instead; it is read on
- * every sort (not cached) so a test can flip it in-process. */
-static bool stream_uniform_gate(const RecTable& rt) {
-  const char* e = getenv("TZS_STREAM_UNIFORM");
-  if (e && e[0] == '0') return false;
-  return rt.nspills == 1 && rt.key_type == 0 && rt.rec_u0 != 0 &&
-         rt.klen_u0 >= 4 && rt.klen_u0 <= rt.rec_u0 && rt.rec_u0 % 4 == 0 &&
-         rt.rec_u0 <= 128 && ((uintptr_t)rt.data0 & 15) == 0;
+/* refinement start byte within the comparator's byte source: sorted-covered
+ * bits are 8*SB - pbits (content mode) or 8*SB - pbits - proxy_w past the
+ * proxy (serialized mode; the proxy is rechecked implicitly because
+ * serialized bytes repeat the content after the 4B length) */
+static int refine_start_byte(const SortParams& p, int pbits) {
+  int c0 = p.ser_mode ? (8 * p.SB - pbits - p.proxy_w) / 8 : (8 * p.SB - pbits) / 8;
+  return c0 < 0 ? 0 : c0;
 }
 
-/* Gate of k_post_sort_meta and the tile skip in k_refine_compact_lb.
- * TZS_POST_FUSE=0 selects the separate k_eq_init / k_count_nonzero_u8 /
- * k_part_hist passes and an unskipped compaction; read on every sort, like
- * TZS_STREAM_UNIFORM. */
-static bool post_fuse_gate() {
-  const char* e = getenv("TZS_POST_FUSE");
-  return !(e && e[0] == '0');
+/* sp->skey / skey2 / sidxb now hold a sorted order built under (p, c0) */
+static void mark_sorted_retained(SpillData* sp, const SortParams& p, int c0) {
+  sp->lo_c0 = c0;
+  sp->sort_sb = p.SB;
+  sp->sort_ser_mode = p.ser_mode;
+  sp->sorted_valid = 1;
 }
 
 /* CRC32 of P device ranges into d_partcrc[P]: super-chunk layout (the one
@@ -4491,177 +4010,104 @@ static int crc_ranges_launch(const uint8_t* d_stream, const uint64_t* d_start,
   return 0;
 }
 
-/* ---- the core: sort current buffer + emit IFile segments ---- */
-static int sort_and_emit(tzs_sorter* s, HostRT& hrt, uint32_t n,
-                         const int32_t* d_part_unsorted,
-                         const uint8_t* h_spill_rle, int nspills_rle,
-                         SpillData* outsp, bool apply_combine = false,
-                         SpillData* retain = nullptr) {
-  tzs_times& T = s->times;
-  g_scatter_ns = 0; g_scatter_launches = 0; g_scatter_elems = 0;
-  hipEvent_t ev[4];
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  (void)hipEventRecord(ev[0]);
+/* ---- refinement + combiner + IFile emit + CRC over an already-ordered view,
+ * one function per stage, called in order by refine_and_emit ---- */
 
-  RecTable rt = hrt.rt;
-  int P = s->conf.num_partitions;
-  int pbits = s->pbits;
-  SortParams prm = derive_sort_params(s, hrt.segs, n);
-  int ser_mode = prm.ser_mode, SB = prm.SB;
-  /* 1. composites */
-  if (s->skey.alloc(sizeof(uint64_t) * n)) return -12;
-  if (s->sidx.alloc(sizeof(uint32_t) * n)) return -12;
-  uint64_t* d_key = (uint64_t*)s->skey.p;
-  uint32_t* d_idx = (uint32_t*)s->sidx.p;
-  if (ser_mode == 0 && stream_uniform_gate(rt)) {
-#define TZS_CS_LAUNCH(NV)                                                     \
-  case NV:                                                                    \
-    hipLaunchKernelGGL((k_build_composite_stream<NV>), dim3(grid1d(n)),       \
-                       dim3(BLOCK), (BLOCK / WAVE) * NV * WAVE * 16, 0,       \
-                       rt.data0, d_part_unsorted, P, pbits, SB, rt.rec_u0,    \
-                       rt.klen_u0 - 4, d_key, d_idx, n);                      \
-    break;
-    switch ((rt.rec_u0 + 15) / 16) {
-      TZS_CS_LAUNCH(1) TZS_CS_LAUNCH(2) TZS_CS_LAUNCH(3) TZS_CS_LAUNCH(4)
-      TZS_CS_LAUNCH(5) TZS_CS_LAUNCH(6) TZS_CS_LAUNCH(7) TZS_CS_LAUNCH(8)
+/* the record set the stages work on; the combiner replaces all four */
+struct RecSet {
+  RecTable rt;
+  uint32_t n;
+  std::vector<SegDesc> hsegs;
+  std::vector<uint32_t> hbase;
+};
+
+/* dense level keys in original-record order: built by the refinement when
+ * most records are ambiguous, and handed on to the retention stage when
+ * they are the level-0 keys (same byte range as the retained lo keys) */
+static thread_local DBuf g_lk0;
+
+/* upper bound on the serialized key length over every segment */
+static int max_key_len(const RecSet& v, uint32_t* out) {
+  uint32_t max_klen = 0;
+  bool need_dev = false;
+  for (auto& sd : v.hsegs) {
+    if (sd.klen_u) { if (sd.klen_u > max_klen) max_klen = sd.klen_u; }
+    else need_dev = true;
+  }
+  if (need_dev) {
+    /* non-uniform segments: device reduction over their klen arrays */
+    static thread_local DBuf dmax;
+    if (dmax.alloc(4)) return -12;
+    HIP_CHECK(hipMemsetAsync(dmax.p, 0, 4));
+    for (size_t sp = 0; sp < v.hsegs.size(); sp++) {
+      if (v.hsegs[sp].klen_u) continue;
+      uint32_t cnt = v.hbase[sp + 1] - v.hbase[sp];
+      if (!cnt) continue;
+      hipLaunchKernelGGL(k_max_u32, dim3(grid1d(cnt)), dim3(BLOCK), 0, 0,
+                         v.hsegs[sp].klen, cnt, (uint32_t*)dmax.p);
     }
-#undef TZS_CS_LAUNCH
-  } else
-    hipLaunchKernelGGL(k_build_composite2, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
-                       d_part_unsorted, P, pbits, prm.ref_pb, SB, ser_mode, d_key,
-                       d_idx, n);
-  (void)hipEventRecord(ev[1]);
-
-  /* 2. base radix sort over the top SB bytes of the composite */
-  int rc = radix_sort<uint64_t>(d_key, d_idx, nullptr, n, 8, 8 - SB,
-                                &s->skey, &s->sidx, nullptr);
-  if (rc) return rc;
-  (void)hipEventRecord(ev[2]);
-  (void)hipEventSynchronize(ev[2]);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ev[0], ev[1]); T.composite_ns += (int64_t)(ms * 1e6);
-  (void)hipEventElapsedTime(&ms, ev[1], ev[2]); T.sort_ns += (int64_t)(ms * 1e6);
-  (void)hipEventElapsedTime(&ms, ev[0], ev[2]); T.total_ns += (int64_t)(ms * 1e6);
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return refine_and_emit(s, hrt.segs, hrt.base, rt, n, SB, ser_mode,
-                         h_spill_rle, nspills_rle, outsp, apply_combine,
-                         retain, nullptr);
+    uint32_t dm = 0;
+    HIP_CHECK(hipMemcpy(&dm, dmax.p, 4, hipMemcpyDeviceToHost));
+    if (dm > max_klen) max_klen = dm;
+  }
+  *out = max_klen;
+  return 0;
 }
 
-/* refinement + combiner + IFile emit + CRC over an already-ordered view:
- * s->skey = masked composites in final base-sort order, s->sidx = global
- * record ids.  Entered from sort_and_emit (base radix sort) or from the
- * flush merge path (k_merge_path tree over retained spill orders). */
-static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
-                           std::vector<uint32_t> hbase,
-                           RecTable rt, uint32_t n, int SB, int ser_mode,
-                           const uint8_t* h_spill_rle, int nspills_rle,
-                           SpillData* outsp, bool apply_combine,
-                           SpillData* retain, const uint64_t* d_lo) {
-  tzs_times& T = s->times;
-  hipEvent_t ev[10];
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  int P = s->conf.num_partitions;
-  int pbits = s->pbits;
-  int ref_pb = 1;
-  for (int v2 = P; v2; v2 >>= 1) ref_pb++;
-  int proxy_w = 24 - ref_pb;
-  if (proxy_w < 0) proxy_w = 0;
+struct Refined {
+  uint32_t neq = 0;           /* set eq flags after the last level: eq[i] then
+                                 means full-key-equal to i-1 */
+  std::vector<uint32_t> meta; /* k_post_sort_meta: {neq before level 0,
+                                 pstart[0..P]} */
+  bool lk0_ready = false;     /* g_lk0 holds the level-0 keys for retention */
+};
+
+/* (a) refinement levels over s->skey / s->sidx (masked composites in base-
+ * sort order, global record ids); d_lo: the merged entry path's lo keys.
+ * keep_lk0: a retention stage follows and can use the level-0 keys.
+ * ev_done is recorded behind the last level, before the scratch goes back
+ * to the pool. */
+static int refine_levels(tzs_sorter* s, const RecSet& v, int ser_mode, int c0,
+                         const uint64_t* d_lo, bool keep_lk0, hipEvent_t ev_done,
+                         Refined* out) {
+  const RecTable& rt = v.rt;
+  const uint32_t n = v.n;
+  const int P = s->conf.num_partitions;
   uint64_t* d_key = (uint64_t*)s->skey.p;
   uint32_t* d_idx = (uint32_t*)s->sidx.p;
   int rc = 0;
-  (void)hipEventRecord(ev[2]);
-
-  /* 3. refinement levels */
   if (s->eq.alloc(n)) return -12;
   if (s->parts_sorted.alloc(sizeof(uint32_t) * n)) return -12;
   uint8_t* d_eq = (uint8_t*)s->eq.p;
-  /* fused path: eq, parts, the eq count, the partition starts and the
-     per-tile in-run counts in one pass; one D2H below fetches
-     {neq, pstart[0..P]} */
-  const bool post_fuse = post_fuse_gate();
+  /* eq, parts, the eq count, the partition starts and the per-tile in-run
+     counts in one pass; one D2H below fetches {neq, pstart[0..P]} */
   const uint32_t nb_tiles = nblocks_for(n, SCAN_TILE);
   static thread_local DBuf post_meta, tile_inrun;
-  std::vector<uint32_t> h_meta(P + 2, 0);
-  if (post_fuse) {
-    if (post_meta.alloc(4 * (size_t)(P + 2))) return -12;
-    if (tile_inrun.alloc(4ull * nb_tiles)) return -12;
-    HIP_CHECK(hipMemsetAsync(post_meta.p, 0, 4 * (size_t)(P + 2)));
-    hipLaunchKernelGGL(k_post_sort_meta, dim3(nb_tiles), dim3(BLOCK), 0, 0, d_key,
-                       d_lo, d_eq, pbits, (uint32_t*)s->parts_sorted.p, n, P,
-                       (uint32_t*)post_meta.p, (uint32_t*)tile_inrun.p);
-  } else if (d_lo)
-    hipLaunchKernelGGL(k_eq_init2, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_key,
-                       d_lo, d_eq, pbits, (uint32_t*)s->parts_sorted.p, n);
-  else
-    hipLaunchKernelGGL(k_eq_init, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_key, d_eq,
-                       pbits, (uint32_t*)s->parts_sorted.p, n);
-  /* max content length: for refinement level count */
-  /* refinement start byte within the comparator's byte source: sorted-covered
-     bits are 8*SB - pbits (content mode) or 8*SB - pbits - 24 past the proxy
-     (serialized mode; the proxy is rechecked implicitly because serialized
-     bytes repeat the content after the 4B length) */
-  int c0 = ser_mode ? (8 * SB - pbits - proxy_w) / 8 : (8 * SB - pbits) / 8;
-  if (c0 < 0) c0 = 0;
+  out->meta.assign(P + 2, 0);
+  if (post_meta.alloc(4 * (size_t)(P + 2))) return -12;
+  if (tile_inrun.alloc(4ull * nb_tiles)) return -12;
+  HIP_CHECK(hipMemsetAsync(post_meta.p, 0, 4 * (size_t)(P + 2)));
+  hipLaunchKernelGGL(k_post_sort_meta, dim3(nb_tiles), dim3(BLOCK), 0, 0, d_key,
+                     d_lo, d_eq, s->pbits, (uint32_t*)s->parts_sorted.p, n, P,
+                     (uint32_t*)post_meta.p, (uint32_t*)tile_inrun.p);
   /* the merged-lo entry path already compared 8 more source bytes */
-  int c0_eff = d_lo ? c0 + 8 : c0;
-  /* determine max clen lazily: use a safe cap by scanning klen on host?  We
-     compute it from the conf: key_type BYTES => clen = klen-4 (max over
-     spills).  For TEXT, clen <= klen-1.  Host keeps max_klen per spill. */
+  const int c0_eff = d_lo ? c0 + 8 : c0;
+  /* level count from the longest key: BYTES => clen = klen-4, TEXT =>
+     clen <= klen-1; klen itself is a safe upper bound on both */
   uint32_t max_klen = 0;
-  {
-    /* reduce over d_klen of every spill in rt — small kernel; here use host
-       copy of spill maxima maintained at absorb time.  For simplicity round 1:
-       copy klen array and reduce on host only once per spill (n small) is too
-       slow for 1e8; do a device reduction. */
-    bool need_dev = false;
-    for (size_t sp = 0; sp < hsegs.size(); sp++) {
-      if (hsegs[sp].klen_u) {
-        if (hsegs[sp].klen_u > max_klen) max_klen = hsegs[sp].klen_u;
-      } else {
-        need_dev = true;
-      }
-    }
-    if (need_dev) {
-      static thread_local DBuf dmax;
-      if (dmax.alloc(4)) return -12;
-      HIP_CHECK(hipMemsetAsync(dmax.p, 0, 4));
-      for (size_t sp = 0; sp < hsegs.size(); sp++) {
-        if (hsegs[sp].klen_u) continue;
-        uint32_t cnt = hbase[sp + 1] - hbase[sp];
-        if (!cnt) continue;
-        hipLaunchKernelGGL(k_max_u32, dim3(grid1d(cnt)), dim3(BLOCK), 0, 0,
-                           hsegs[sp].klen, cnt, (uint32_t*)dmax.p);
-      }
-      uint32_t dm = 0;
-      HIP_CHECK(hipMemcpy(&dm, dmax.p, 4, hipMemcpyDeviceToHost));
-      if (dm > max_klen) max_klen = dm;
-    }
-  }
-  int max_clen = (int)max_klen; /* upper bound on content length */
+  if ((rc = max_key_len(v, &max_klen))) return rc;
+  const int max_clen = (int)max_klen;
   static thread_local DBuf eqcnt;
   static thread_local DBuf lkey, seg, pos, slotpos;
-  static thread_local DBuf lk0;
+  DBuf& lk0 = g_lk0;
   if (eqcnt.alloc(4)) return -12;
 
-  bool will_combine = apply_combine && s->conf.combiner == 1;
-  bool lk0_retain_ready = false; /* dense level-0 keys double as the lo
-                                    retention source (same byte range) */
-  int level = 1;
   const int max_levels = (max_clen > c0_eff) ? (max_clen - c0_eff + 7) / 8 : 0;
   /* initial ambiguity count; later levels get it from k_eq_update's
      survivor counter (saves a full-n read per level) */
-  uint32_t neq = 0;
-  if (post_fuse) {
-    HIP_CHECK(hipMemcpy(h_meta.data(), post_meta.p, 4 * (size_t)(P + 2),
-                        hipMemcpyDeviceToHost));
-    neq = h_meta[0];
-  } else {
-    HIP_CHECK(hipMemsetAsync(eqcnt.p, 0, 4));
-    hipLaunchKernelGGL(k_count_nonzero_u8, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_eq, n,
-                       (uint32_t*)eqcnt.p);
-    HIP_CHECK(hipMemcpy(&neq, eqcnt.p, 4, hipMemcpyDeviceToHost));
-  }
+  HIP_CHECK(hipMemcpy(out->meta.data(), post_meta.p, 4 * (size_t)(P + 2),
+                      hipMemcpyDeviceToHost));
+  uint32_t neq = out->meta[0];
   for (int li = 0; li <= max_levels; li++) {
     if (neq == 0) break;
     int use_len = (li == max_levels); /* final tiebreak: content length */
@@ -4680,9 +4126,9 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
          n <= 3e8: the 8n-byte lk0 buffer at a 1e9-record merge pushed the
          peak working set into pool-drop/hipMalloc churn. */
       const uint64_t* lk0p = nullptr;
-      /* !lk0_retain_ready: a later level must not overwrite the retained
-         level-0 content (it gathers through sidx after the loop) */
-      if (3ull * neq >= n && n <= 300000000u && !lk0_retain_ready) {
+      /* !lk0_ready: a later level must not overwrite the retained level-0
+         content (the retention stage gathers it through sidx) */
+      if (3ull * neq >= n && n <= 300000000u && !out->lk0_ready) {
         if (lk0.alloc(8ull * n)) return -12;
         hipLaunchKernelGGL(k_build_lkeys, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
                            lb0, use_len, ser_mode, (uint64_t*)lk0.p, n);
@@ -4699,7 +4145,7 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
          positions are in a run, so with neq >= n/16 (Text keys, C3) at
          least every eighth position may be and the per-block tile_inrun
          load buys nothing */
-      const bool skip_tiles = post_fuse && (uint64_t)neq * 16 < n;
+      const bool skip_tiles = (uint64_t)neq * 16 < n;
       hipLaunchKernelGGL(k_refine_compact_lb, dim3(nb_rc), dim3(BLOCK), 0, 0, rt,
                          d_idx, d_eq, n, lb0, use_len, ser_mode, lk0p,
                          (uint64_t*)lkey.p, (uint32_t*)seg.p, (uint32_t*)pos.p,
@@ -4710,9 +4156,9 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
       HIP_CHECK(hipMemcpy(hh, rc_tick.p, 24, hipMemcpyDeviceToHost));
       if ((uint32_t)(hh[0] >> 32)) FAIL(-70, "refine compact lookback timeout");
       ptotal = hh[2];
-      if (li == 0 && !use_len && lk0p && retain && !will_combine)
-        lk0_retain_ready = true; /* keep the buffer for retention below */
-      else if (!lk0_retain_ready)
+      if (li == 0 && !use_len && lk0p && keep_lk0)
+        out->lk0_ready = true; /* keep the buffer for the retention stage */
+      else if (!out->lk0_ready)
         lk0.release();
     }
     uint64_t nruns = ptotal & 0xFFFFFFFFu;
@@ -4746,51 +4192,51 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
                        (const uint64_t*)lkey.p, (const uint32_t*)seg.p,
                        (const uint32_t*)slotpos.p, d_eq, m, (uint32_t*)eqcnt.p);
     HIP_CHECK(hipMemcpy(&neq, eqcnt.p, 4, hipMemcpyDeviceToHost));
-    level++;
   }
-  (void)hipEventRecord(ev[3]);
-  /* large-n headroom: refinement scratch and radix ping-pong temps are dead
-     from here; return them to the pool before the output-stream allocation
-     (at C3's 1e9 records these hold ~60 GB) */
+  (void)hipEventRecord(ev_done);
+  /* large-n headroom: the level scratch is dead from here; return it to the
+     pool before the output-stream allocation (at C3's 1e9 records it and
+     the radix ping-pong temps hold ~60 GB) */
   lkey.release(); seg.release(); pos.release(); slotpos.release();
-  radix_release_temps();
+  out->neq = neq;
+  return 0;
+}
 
-  /* retain the refined sorted order for the flush merge path (VERDICT r1
-     #1): composites move out (nothing below reads them), sorted ids are
-     copied (s->sidx stays live for emit + sorted_columnar).  Combiner
-     spills retain the FOLDED set instead (built in the combiner branch). */
-  if (retain && !will_combine) {
-    std::swap(retain->skey, s->skey);
-    if (retain->sidxb.alloc(4ull * n)) return -12;
-    HIP_CHECK(hipMemcpyAsync(retain->sidxb.p, s->sidx.p, 4ull * n,
-                             hipMemcpyDeviceToDevice));
-    /* lo keys: comparator-source bytes [c0, c0+8) per sorted record — the
-       refinement's dense level-0 build is the same array when it ran;
-       otherwise build it now, then one 8B gather into sorted order */
-    if (retain->skey2.alloc(8ull * n)) return -12;
-    {
-      if (!lk0_retain_ready) {
-        if (lk0.alloc(8ull * n)) return -12;
-        hipLaunchKernelGGL(k_build_lkeys, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
-                           c0, 0, ser_mode, (uint64_t*)lk0.p, n);
-      }
-      hipLaunchKernelGGL(k_gather_merge_hi, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
-                         (const uint64_t*)lk0.p, (const uint32_t*)s->sidx.p,
-                         (uint64_t*)retain->skey2.p, 0ull, n);
-      lk0.release();
-    }
-    retain->lo_c0 = c0;
-    retain->sort_sb = SB;
-    retain->sort_ser_mode = ser_mode;
-    retain->sorted_valid = 1;
+/* (b) retain the refined sorted order for the flush merge path: composites
+ * move out of s->skey (nothing later reads them), sorted ids are copied
+ * (s->sidx stays live for emit + sorted_columnar).  Combiner spills retain
+ * the FOLDED set instead (combine_fold). */
+static int retain_sorted_order(tzs_sorter* s, const RecTable& rt, uint32_t n,
+                               const SortParams& prm, int c0, bool lk0_ready,
+                               SpillData* retain) {
+  DBuf& lk0 = g_lk0;
+  std::swap(retain->skey, s->skey);
+  if (retain->sidxb.alloc(4ull * n)) return -12;
+  HIP_CHECK(hipMemcpyAsync(retain->sidxb.p, s->sidx.p, 4ull * n,
+                           hipMemcpyDeviceToDevice));
+  /* lo keys: comparator-source bytes [c0, c0+8) per sorted record — the
+     refinement's dense level-0 build is the same array when it ran;
+     otherwise build it now, then one 8B gather into sorted order */
+  if (retain->skey2.alloc(8ull * n)) return -12;
+  if (!lk0_ready) {
+    if (lk0.alloc(8ull * n)) return -12;
+    hipLaunchKernelGGL(k_build_lkeys, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
+                       c0, 0, prm.ser_mode, (uint64_t*)lk0.p, n);
   }
+  hipLaunchKernelGGL(k_gather_merge_hi, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
+                     (const uint64_t*)lk0.p, (const uint32_t*)s->sidx.p,
+                     (uint64_t*)retain->skey2.p, 0ull, n);
+  lk0.release();
+  mark_sorted_retained(retain, prm, c0);
+  return 0;
+}
 
-  /* 4. writer-rle decision + same flags (neq carried out of the refinement
-     loop — after the final level eq[i] means full-key-equal) */
-  uint32_t neq_final = neq;
-  int writer_rle;
+/* (c) writer-RLE decision from the final eq flags (neq of them set) */
+static int decide_writer_rle(tzs_sorter* s, const RecTable& rt, uint32_t n,
+                             uint32_t neq, const uint8_t* h_spill_rle,
+                             int nspills_rle, int* writer_rle) {
   if (s->conf.rle >= 0) {
-    writer_rle = s->conf.rle;
+    *writer_rle = s->conf.rle;
   } else if (nspills_rle > 1) {
     /* multi-spill merge: the auto gate counts SAME_KEY machine events —
        equal keys meeting ACROSS segments or carried by an RLE'd source
@@ -4799,193 +4245,219 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
        within-spill duplicates sat below each spill's own gate).  Computed
        by running the provenance kernel with writer_rle=0 and counting. */
     if (s->same.alloc(n)) return -12;
-    {
-      static thread_local DBuf d_sprle0, cnt0;
-      if (d_sprle0.alloc(nspills_rle)) return -12;
-      if (cnt0.alloc(4)) return -12;
-      HIP_CHECK(hipMemcpyAsync(d_sprle0.p, h_spill_rle, nspills_rle,
-                               hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(k_writer_same, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
-                         d_idx, d_eq, 0, (const uint8_t*)d_sprle0.p,
-                         (uint8_t*)s->same.p, n);
-      HIP_CHECK(hipMemsetAsync(cnt0.p, 0, 4));
-      hipLaunchKernelGGL(k_count_nonzero_u8, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
-                         (const uint8_t*)s->same.p, n, (uint32_t*)cnt0.p);
-      uint32_t ev = 0;
-      HIP_CHECK(hipMemcpy(&ev, cnt0.p, 4, hipMemcpyDeviceToHost));
-      writer_rle = ((uint64_t)ev * 10 > n) ? 1 : 0;
-    }
+    static thread_local DBuf d_sprle0, cnt0;
+    if (d_sprle0.alloc(nspills_rle)) return -12;
+    if (cnt0.alloc(4)) return -12;
+    HIP_CHECK(hipMemcpyAsync(d_sprle0.p, h_spill_rle, nspills_rle,
+                             hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_writer_same, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
+                       (const uint32_t*)s->sidx.p, (const uint8_t*)s->eq.p, 0,
+                       (const uint8_t*)d_sprle0.p, (uint8_t*)s->same.p, n);
+    HIP_CHECK(hipMemsetAsync(cnt0.p, 0, 4));
+    hipLaunchKernelGGL(k_count_nonzero_u8, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
+                       (const uint8_t*)s->same.p, n, (uint32_t*)cnt0.p);
+    uint32_t events = 0;
+    HIP_CHECK(hipMemcpy(&events, cnt0.p, 4, hipMemcpyDeviceToHost));
+    *writer_rle = ((uint64_t)events * 10 > n) ? 1 : 0;
   } else {
     /* single spill: adjacent-equal pairs in sorted order */
-    writer_rle = ((uint64_t)neq_final * 10 > n) ? 1 : 0;
+    *writer_rle = ((uint64_t)neq * 10 > n) ? 1 : 0;
   }
+  return 0;
+}
 
-  /* combiner stage: replace the sorted view with folded records */
-  s->combine_applied = false;
-  if (apply_combine && s->conf.combiner == 1) {
-    /* partitions of the sorted records (parts_sorted, from k_eq_init) */
-    static thread_local DBuf rs, rs_scan, pos2, lens2, off2, parts2, idx2;
-    if (rs.alloc(8ull * n) || rs_scan.alloc(8ull * n)) return -12;
-    hipLaunchKernelGGL(k_combine_mark, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_eq,
-                       (uint64_t*)rs.p, n);
-    uint64_t M64 = 0;
-    if (scan_u64((uint64_t*)rs.p, (uint64_t*)rs_scan.p, n, &M64)) return -12;
-    uint32_t M = (uint32_t)M64;
-    if (pos2.alloc(4ull * M) || lens2.alloc(8ull * M) || off2.alloc(8ull * (M + 1)))
-      return -12;
-    hipLaunchKernelGGL(k_combine_pos, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_eq,
-                       (const uint64_t*)rs_scan.p, (uint32_t*)pos2.p,
-                       (uint64_t*)lens2.p, rt, d_idx, n);
-    uint64_t bytes2 = 0;
-    if (scan_u64((uint64_t*)lens2.p, (uint64_t*)off2.p, M, &bytes2)) return -12;
-    HIP_CHECK(hipMemcpy((uint64_t*)off2.p + M, &bytes2, 8, hipMemcpyHostToDevice));
-    if (s->combine_data.alloc(bytes2 ? bytes2 : 1)) return -12;
-    if (s->combine_klen.alloc(4ull * M)) return -12;
-    if (parts2.alloc(4ull * M) || idx2.alloc(4ull * M)) return -12;
-    hipLaunchKernelGGL(k_combine_fold, dim3(grid_waves(M)), dim3(BLOCK), 0, 0, rt,
-                       d_idx, (const uint32_t*)pos2.p, (const uint64_t*)off2.p,
-                       (const uint32_t*)s->parts_sorted.p, (uint8_t*)s->combine_data.p,
-                       (uint32_t*)s->combine_klen.p, (uint32_t*)parts2.p, M, n);
-    /* swap the view: single-"spill" table over the folded records */
-    std::swap(s->combine_off, off2);
-    RecTable rt2 = {};
-    rt2.nspills = 1;
-    rt2.data0 = (const uint8_t*)s->combine_data.p;
-    rt2.off0 = (const uint64_t*)s->combine_off.p;
-    rt2.klen0 = (const uint32_t*)s->combine_klen.p;
-    rt2.n0 = M;
-    rt2.key_type = rt.key_type;
-    rt = rt2;
-    n = M;
-    SegDesc csd;
-    csd.data = rt2.data0; csd.off = rt2.off0; csd.klen = rt2.klen0;
-    csd.rec_u = 0; csd.klen_u = 0;
-    hsegs.assign(1, csd);
-    hbase.assign(2, 0);
-    hbase[1] = M;
-    hipLaunchKernelGGL(k_iota, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
-                       (uint32_t*)idx2.p, n);
-    std::swap(s->sidx, idx2);
-    d_idx = (uint32_t*)s->sidx.p;
-    if (s->eq.alloc(n)) return -12;
-    d_eq = (uint8_t*)s->eq.p;
-    HIP_CHECK(hipMemsetAsync(d_eq, 0, n));
-    std::swap(s->parts_sorted, parts2);
-    writer_rle = 0; /* folded keys are unique; rle never triggers */
-    s->combined_parts_valid = true;
-    s->combine_applied = true;
-    s->combine_n = M;
-    if (retain) {
-      /* folded records are stored in sorted order: identity ids, composites
-         rebuilt in order over the folded table (coalesced) */
-      s->skey.release();
-      if (retain->skey.alloc(8ull * n)) return -12;
-      if (retain->sidxb.alloc(4ull * n)) return -12;
-      hipLaunchKernelGGL(k_build_composite, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
-                         rt, (const int32_t*)s->parts_sorted.p, P, pbits,
-                         ref_pb, SB, ser_mode, (uint64_t*)retain->skey.p,
-                         (uint32_t*)retain->sidxb.p, n);
-      if (retain->skey2.alloc(8ull * n)) return -12;
-      hipLaunchKernelGGL(k_build_lkeys, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
-                         c0, 0, ser_mode, (uint64_t*)retain->skey2.p, n);
-      retain->lo_c0 = c0;
-      retain->sort_sb = SB;
-      retain->sort_ser_mode = ser_mode;
-      retain->sorted_valid = 1;
-    }
-  } else {
-    s->combined_parts_valid = false;
+/* (d) combiner: fold each run of equal keys into one record and replace the
+ * sorted view (*v, s->sidx, s->eq, s->parts_sorted) with the folded set,
+ * which is stored in sorted order.  retain (nullable) gets that set's
+ * sorted state. */
+static int combine_fold(tzs_sorter* s, RecSet* v, const SortParams& prm, int c0,
+                        SpillData* retain) {
+  const RecTable& rt = v->rt;
+  uint32_t n = v->n;
+  const uint32_t* d_idx = (const uint32_t*)s->sidx.p;
+  const uint8_t* d_eq = (const uint8_t*)s->eq.p;
+  static thread_local DBuf rs, rs_scan, pos2, lens2, off2, parts2, idx2;
+  if (rs.alloc(8ull * n) || rs_scan.alloc(8ull * n)) return -12;
+  hipLaunchKernelGGL(k_combine_mark, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_eq,
+                     (uint64_t*)rs.p, n);
+  uint64_t M64 = 0;
+  if (scan_u64((uint64_t*)rs.p, (uint64_t*)rs_scan.p, n, &M64)) return -12;
+  uint32_t M = (uint32_t)M64;
+  if (pos2.alloc(4ull * M) || lens2.alloc(8ull * M) || off2.alloc(8ull * (M + 1)))
+    return -12;
+  hipLaunchKernelGGL(k_combine_pos, dim3(grid1d(n)), dim3(BLOCK), 0, 0, d_eq,
+                     (const uint64_t*)rs_scan.p, (uint32_t*)pos2.p,
+                     (uint64_t*)lens2.p, rt, d_idx, n);
+  uint64_t bytes2 = 0;
+  if (scan_u64((uint64_t*)lens2.p, (uint64_t*)off2.p, M, &bytes2)) return -12;
+  HIP_CHECK(hipMemcpy((uint64_t*)off2.p + M, &bytes2, 8, hipMemcpyHostToDevice));
+  if (s->combine_data.alloc(bytes2 ? bytes2 : 1)) return -12;
+  if (s->combine_klen.alloc(4ull * M)) return -12;
+  if (parts2.alloc(4ull * M) || idx2.alloc(4ull * M)) return -12;
+  hipLaunchKernelGGL(k_combine_fold, dim3(grid_waves(M)), dim3(BLOCK), 0, 0, rt,
+                     d_idx, (const uint32_t*)pos2.p, (const uint64_t*)off2.p,
+                     (const uint32_t*)s->parts_sorted.p, (uint8_t*)s->combine_data.p,
+                     (uint32_t*)s->combine_klen.p, (uint32_t*)parts2.p, M, n);
+  /* swap the view: single-"spill" table over the folded records */
+  std::swap(s->combine_off, off2);
+  RecTable rt2 = {};
+  rt2.nspills = 1;
+  rt2.data0 = (const uint8_t*)s->combine_data.p;
+  rt2.off0 = (const uint64_t*)s->combine_off.p;
+  rt2.klen0 = (const uint32_t*)s->combine_klen.p;
+  rt2.n0 = M;
+  rt2.key_type = rt.key_type;
+  v->rt = rt2;
+  v->n = n = M;
+  SegDesc csd;
+  csd.data = rt2.data0; csd.off = rt2.off0; csd.klen = rt2.klen0;
+  csd.rec_u = 0; csd.klen_u = 0;
+  v->hsegs.assign(1, csd);
+  v->hbase.assign(2, 0);
+  v->hbase[1] = M;
+  hipLaunchKernelGGL(k_iota, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
+                     (uint32_t*)idx2.p, n);
+  std::swap(s->sidx, idx2);
+  if (s->eq.alloc(n)) return -12;
+  HIP_CHECK(hipMemsetAsync(s->eq.p, 0, n));
+  std::swap(s->parts_sorted, parts2);
+  s->combined_parts_valid = true;
+  s->combine_applied = true;
+  s->combine_n = M;
+  if (retain) {
+    /* folded records are stored in sorted order: identity ids, composites
+       rebuilt in order over the folded table (coalesced) */
+    s->skey.release();
+    if (retain->skey.alloc(8ull * n)) return -12;
+    if (retain->sidxb.alloc(4ull * n)) return -12;
+    hipLaunchKernelGGL(k_build_composite, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
+                       v->rt, (const int32_t*)s->parts_sorted.p,
+                       s->conf.num_partitions, s->pbits, prm.ref_pb, prm.SB,
+                       prm.ser_mode, (uint64_t*)retain->skey.p,
+                       (uint32_t*)retain->sidxb.p, n);
+    if (retain->skey2.alloc(8ull * n)) return -12;
+    hipLaunchKernelGGL(k_build_lkeys, dim3(grid1d(n)), dim3(BLOCK), 0, 0, v->rt,
+                       c0, 0, prm.ser_mode, (uint64_t*)retain->skey2.p, n);
+    mark_sorted_retained(retain, prm, c0);
   }
+  return 0;
+}
+
+/* same_writer flags for the final view (see k_writer_same) */
+static int writer_same_flags(tzs_sorter* s, const RecTable& rt, uint32_t n,
+                             int writer_rle, const uint8_t* h_spill_rle,
+                             int nspills_rle) {
   if (s->same.alloc(n)) return -12;
   static thread_local DBuf d_sprle;
   if (d_sprle.alloc(nspills_rle ? nspills_rle : 1)) return -12;
   if (nspills_rle)
     HIP_CHECK(hipMemcpy(d_sprle.p, h_spill_rle, nspills_rle, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_writer_same, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt, d_idx, d_eq,
+  hipLaunchKernelGGL(k_writer_same, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
+                     (const uint32_t*)s->sidx.p, (const uint8_t*)s->eq.p,
                      writer_rle, (const uint8_t*)d_sprle.p, (uint8_t*)s->same.p, n);
+  return 0;
+}
 
-  /* uniform-emit gate: constant record serialization + RLE provably off */
-  uint32_t uni_rec = 0, uni_klen = 0;
-  {
-    bool uni = !hsegs.empty() && !s->combine_applied;
-    for (size_t sp2 = 0; sp2 < hsegs.size() && uni; sp2++) {
-      if (!hsegs[sp2].rec_u || !hsegs[sp2].klen_u) uni = false;
-      else if (sp2 == 0) { uni_rec = hsegs[0].rec_u; uni_klen = hsegs[0].klen_u; }
-      else if (uni_rec != hsegs[sp2].rec_u || uni_klen != hsegs[sp2].klen_u)
-        uni = false;
-    }
-    if (!uni) uni_rec = 0;
-  }
-  bool no_same = (writer_rle == 0) &&
-      (neq_final == 0 || (nspills_rle == 1 && h_spill_rle && !h_spill_rle[0]));
-  uint32_t uh_len = 0;
-  uint64_t uh_word = 0;
-  if (uni_rec && no_same) {
-    uint8_t hb[12] = {0};
-    auto hvint = [](uint8_t* b, uint32_t v) -> uint32_t {
-      if (v <= 127) { b[0] = (uint8_t)v; return 1; }
-      uint32_t nb2 = 0, t = v;
-      while (t) { t >>= 8; nb2++; }
-      b[0] = (uint8_t)(-112 - (int)nb2);
-      for (uint32_t k = 0; k < nb2; k++) b[1 + k] = (uint8_t)(v >> (8 * (nb2 - 1 - k)));
-      return 1 + nb2;
-    };
-    uh_len = hvint(hb, uni_klen);
-    uh_len += hvint(hb + uh_len, uni_rec - uni_klen);
-    for (int b = 0; b < 8; b++) uh_word |= (uint64_t)hb[b] << (8 * b);
-    if (uh_len > 8) uni_rec = 0; /* header too long for the fast paths */
-  }
-  /* single-segment uniform no-RLE: src/dst/sizes are pure arithmetic — skip
-     the descriptor build, the size scan AND the per-partition scan gather */
-  bool arith_emit = rt.nspills == 1 && uni_rec && no_same;
+/* hadoop vint (WritableUtils) of a non-negative length */
+static uint32_t h_vint_write(uint8_t* b, uint32_t v) {
+  if (v <= 127) { b[0] = (uint8_t)v; return 1; }
+  uint32_t nb = 0, t = v;
+  while (t) { t >>= 8; nb++; }
+  b[0] = (uint8_t)(-112 - (int)nb);
+  for (uint32_t k = 0; k < nb; k++) b[1 + k] = (uint8_t)(v >> (8 * (nb - 1 - k)));
+  return 1 + nb;
+}
 
-  /* 5. emit sizes + partition layout (parts_sorted came from k_eq_init; the
-     combiner path swapped in its own parts2) */
+/* constant record serialization with RLE provably off: every record is
+ * hdr_len header bytes (hdr_word, little-endian) + rec bytes.  rec == 0:
+ * not uniform, or the header does not fit the 8-byte word. */
+struct UniformEmit { uint32_t rec = 0, hdr_len = 0; uint64_t hdr_word = 0; };
+static UniformEmit uniform_emit_gate(const RecSet& v, bool combined, bool no_same) {
+  UniformEmit u;
+  if (v.hsegs.empty() || combined || !no_same) return u;
+  uint32_t rec = v.hsegs[0].rec_u, klen = v.hsegs[0].klen_u;
+  for (auto& sd : v.hsegs)
+    if (!sd.rec_u || !sd.klen_u || sd.rec_u != rec || sd.klen_u != klen) return u;
+  uint8_t hb[12] = {0};
+  u.hdr_len = h_vint_write(hb, klen);
+  u.hdr_len += h_vint_write(hb + u.hdr_len, rec - klen);
+  for (int b = 0; b < 8; b++) u.hdr_word |= (uint64_t)hb[b] << (8 * b);
+  if (u.hdr_len <= 8) u.rec = rec;
+  return u;
+}
+
+/* per-partition segment layout of the output stream: host copy, device
+ * copies, the record descriptors (null for the arithmetic emit) and the
+ * stream itself.  Stage (e) fills it, (f) and (g) read it. */
+struct EmitLayout {
+  std::vector<uint64_t> seg_start, body, payload_start, scanbase, range_start,
+      range_len;
+  std::vector<uint8_t> last_same, present;
+  const uint64_t *d_pstart = nullptr, *d_segstart = nullptr, *d_body = nullptr,
+                 *d_paystart = nullptr, *d_scanbase = nullptr,
+                 *d_rstart = nullptr, *d_rlen = nullptr;
+  const uint8_t *d_lastsame = nullptr, *d_present = nullptr;
+  const RecDesc* d_desc = nullptr;
+  uint8_t* d_out = nullptr;
+};
+
+/* (e1) record descriptors, emit sizes and their scan (s->scan) */
+static int emit_sizes(tzs_sorter* s, const RecSet& v, const RecDesc** d_desc,
+                      uint64_t* total_body) {
+  const RecTable& rt = v.rt;
+  const uint32_t n = v.n;
+  const uint32_t* d_idx = (const uint32_t*)s->sidx.p;
   static thread_local DBuf descbuf;
-  uint64_t total_body = 0;
-  if (!arith_emit) {
   if (descbuf.alloc(sizeof(RecDesc) * n)) return -12;
   if (s->sizes.alloc(sizeof(uint64_t) * n)) return -12;
   if (s->scan.alloc(sizeof(uint64_t) * n)) return -12;
-  {
-    bool direct = rt.key_type != 1;
-    for (auto& sd : hsegs)
-      if (!sd.rec_u) { direct = false; break; }
-    if (direct) {
-      /* uniform BytesWritable tables: rt_view is pure arithmetic; emit
-         sizes are computed in the same pass */
-      hipLaunchKernelGGL(k_build_desc, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt, d_idx,
-                         (RecDesc*)descbuf.p, (const uint8_t*)s->same.p,
-                         (const uint32_t*)s->parts_sorted.p,
-                         (uint64_t*)s->sizes.p, n);
-    } else {
-      /* variable-length / Text: build in original order (coalesced off/klen/
-         vint reads), then one 16B-per-record permute + fused sizes */
-      static thread_local DBuf desc0;
-      if (desc0.alloc(sizeof(RecDesc) * n)) return -12;
-      hipLaunchKernelGGL(k_build_desc, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
-                         (const uint32_t*)nullptr, (RecDesc*)desc0.p,
-                         (const uint8_t*)nullptr, (const uint32_t*)nullptr,
-                         (uint64_t*)nullptr, n);
-      hipLaunchKernelGGL(k_permute_desc, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
-                         (const RecDesc*)desc0.p, d_idx, (RecDesc*)descbuf.p,
-                         (const uint8_t*)s->same.p,
-                         (const uint32_t*)s->parts_sorted.p,
-                         (uint64_t*)s->sizes.p, n);
-      desc0.release();
-    }
-  }
-  if (scan_u64((uint64_t*)s->sizes.p, (uint64_t*)s->scan.p, n, &total_body)) return -12;
-  s->sizes.release();
+  bool direct = rt.key_type != 1;
+  for (auto& sd : v.hsegs)
+    if (!sd.rec_u) { direct = false; break; }
+  if (direct) {
+    /* uniform BytesWritable tables: rt_view is pure arithmetic; emit
+       sizes are computed in the same pass */
+    hipLaunchKernelGGL(k_build_desc, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt, d_idx,
+                       (RecDesc*)descbuf.p, (const uint8_t*)s->same.p,
+                       (const uint32_t*)s->parts_sorted.p,
+                       (uint64_t*)s->sizes.p, n);
   } else {
-    total_body = (uint64_t)n * (uh_len + uni_rec);
+    /* variable-length / Text: build in original order (coalesced off/klen/
+       vint reads), then one 16B-per-record permute + fused sizes */
+    static thread_local DBuf desc0;
+    if (desc0.alloc(sizeof(RecDesc) * n)) return -12;
+    hipLaunchKernelGGL(k_build_desc, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
+                       (const uint32_t*)nullptr, (RecDesc*)desc0.p,
+                       (const uint8_t*)nullptr, (const uint32_t*)nullptr,
+                       (uint64_t*)nullptr, n);
+    hipLaunchKernelGGL(k_permute_desc, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
+                       (const RecDesc*)desc0.p, d_idx, (RecDesc*)descbuf.p,
+                       (const uint8_t*)s->same.p,
+                       (const uint32_t*)s->parts_sorted.p,
+                       (uint64_t*)s->sizes.p, n);
+    desc0.release();
   }
-  s->skey.release();  /* composites are dead once parts_sorted exists */
+  if (scan_u64((uint64_t*)s->sizes.p, (uint64_t*)s->scan.p, n, total_body)) return -12;
+  s->sizes.release();
+  *d_desc = (const RecDesc*)descbuf.p;
+  return 0;
+}
+
+/* (e2) partition record ranges, host segment layout, index records and the
+ * output stream allocation.  meta: the partition starts taken before the
+ * combiner, valid unless it ran.  uni (nullable): the arithmetic emit's
+ * record shape; otherwise body sizes come from s->scan. */
+static int partition_layout(tzs_sorter* s, const RecSet& v,
+                            const std::vector<uint32_t>& meta,
+                            const UniformEmit* uni, uint64_t total_body,
+                            SpillData* outsp, EmitLayout* L) {
+  const int P = s->conf.num_partitions;
+  const uint32_t n = v.n;
   /* partition record ranges: host-side from a partition histogram */
   std::vector<uint32_t> h_pcount(P, 0);
-  if (post_fuse && !s->combine_applied) {
+  if (!s->combine_applied) {
     /* sorted order: a partition's count is the distance between two starts */
-    for (int p = 0; p < P; p++) h_pcount[p] = h_meta[2 + p] - h_meta[1 + p];
+    for (int p = 0; p < P; p++) h_pcount[p] = meta[2 + p] - meta[1 + p];
   } else {
     /* the combiner replaced n and parts_sorted: the starts taken before it
        no longer describe the view */
@@ -5001,20 +4473,20 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
   std::vector<uint64_t> h_prec_start(P + 1, 0);
   for (int p = 0; p < P; p++) h_prec_start[p + 1] = h_prec_start[p] + h_pcount[p];
   s->final_rec_ranges = h_prec_start;
-  s->final_rt = rt;
+  s->final_rt = v.rt;
   s->final_n = n;
-  /* body bytes per partition = scan[start of next] - scan[start] */
-  /* gather per-partition scan bases + last-same flags in one kernel +
-     one D2H (was 2P+1 synchronous 8-byte copies) */
+  /* body bytes per partition = scan[start of next] - scan[start]: gather
+     per-partition scan bases + last-same flags in one kernel + one D2H */
   std::vector<uint64_t> h_scan_at(P + 1, 0);
-  std::vector<uint8_t> h_last_same(P, 0);
+  L->last_same.assign(P, 0);
   static thread_local DBuf d_pstart;
   if (d_pstart.alloc(8 * (P + 1))) return -12;
   HIP_CHECK(hipMemcpyAsync(d_pstart.p, h_prec_start.data(), 8 * (P + 1),
                            hipMemcpyHostToDevice));
-  if (arith_emit) {
+  L->d_pstart = (const uint64_t*)d_pstart.p;
+  if (uni) {
     for (int p = 0; p <= P; p++)
-      h_scan_at[p] = h_prec_start[p] * (uint64_t)(uh_len + uni_rec);
+      h_scan_at[p] = h_prec_start[p] * (uint64_t)(uni->hdr_len + uni->rec);
   } else {
     static thread_local DBuf d_gathered;
     if (d_gathered.alloc(16 * (P + 1))) return -12;
@@ -5026,164 +4498,244 @@ static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
     HIP_CHECK(hipMemcpy(tmp.data(), d_gathered.p, 16 * (P + 1), hipMemcpyDeviceToHost));
     for (int p = 0; p <= P; p++) h_scan_at[p] = tmp[2 * p];
     for (int p = 0; p < P; p++)
-      h_last_same[p] = (h_pcount[p] > 0) ? (uint8_t)tmp[2 * p + 1] : 0;
+      L->last_same[p] = (h_pcount[p] > 0) ? (uint8_t)tmp[2 * p + 1] : 0;
   }
   /* segment layout */
   int send_empty = s->conf.send_empty_partition_details;
-  std::vector<uint64_t> h_seg_start(P, 0), h_body(P, 0), h_range_start(P, 0),
-      h_range_len(P, 0), h_payload_start(P, 0), h_scanbase(P, 0);
-  std::vector<uint8_t> h_present(P, 0);
+  L->seg_start.assign(P, 0); L->body.assign(P, 0); L->range_start.assign(P, 0);
+  L->range_len.assign(P, 0); L->payload_start.assign(P, 0); L->scanbase.assign(P, 0);
+  L->present.assign(P, 0);
   outsp->index.resize(P);
   uint64_t cursor = 0;
   for (int p = 0; p < P; p++) {
     uint64_t body = h_scan_at[p + 1] - h_scan_at[p];
     bool present = (h_pcount[p] > 0) || !send_empty;
-    h_present[p] = present;
-    h_seg_start[p] = cursor;
-    h_body[p] = body;
-    h_payload_start[p] = cursor + 4;
-    h_scanbase[p] = h_scan_at[p];
-    uint64_t tail = (h_last_same[p] ? 1 : 0) + 2; /* V_END? + EOF */
+    L->present[p] = present;
+    L->seg_start[p] = cursor;
+    L->body[p] = body;
+    L->payload_start[p] = cursor + 4;
+    L->scanbase[p] = h_scan_at[p];
+    uint64_t tail = (L->last_same[p] ? 1 : 0) + 2; /* V_END? + EOF */
     int64_t rawl = 0, partl = 0;
     if (present) {
       rawl = 4 + (int64_t)body + (int64_t)tail;
       partl = rawl + 4;
-      h_range_start[p] = cursor + 4;
-      h_range_len[p] = body + tail;
+      L->range_start[p] = cursor + 4;
+      L->range_len[p] = body + tail;
       cursor += (uint64_t)partl;
     }
-    outsp->index[p].start_offset = (int64_t)h_seg_start[p];
+    outsp->index[p].start_offset = (int64_t)L->seg_start[p];
     outsp->index[p].raw_length = rawl;
     outsp->index[p].part_length = partl;
   }
   uint64_t stream_len = cursor;
   if (outsp->ifile.alloc(stream_len ? stream_len + 16 : 1)) return -12;
-  uint8_t* d_out = (uint8_t*)outsp->ifile.p;
+  L->d_out = (uint8_t*)outsp->ifile.p;
   outsp->ifile_len = (int64_t)stream_len;
-  outsp->rle = (uint8_t)writer_rle;
-  (void)hipEventRecord(ev[4]);
+  return 0;
+}
 
-  /* upload layout arrays */
+/* (e3) device copies of the layout arrays */
+static int upload_layout(EmitLayout* L) {
   static thread_local DBuf d_segstart, d_body, d_paystart, d_scanbase, d_lastsame,
-      d_present, d_rstart, d_rlen, d_partcrc;
+      d_present, d_rstart, d_rlen;
+  const size_t P = L->seg_start.size();
   auto up = [&](DBuf& b, const void* src, size_t sz) -> int {
     if (b.alloc(sz)) return -12;
     HIP_CHECK(hipMemcpyAsync(b.p, src, sz, hipMemcpyHostToDevice));
     return 0;
   };
-  if (up(d_segstart, h_seg_start.data(), 8 * P)) return -12;
-  if (up(d_body, h_body.data(), 8 * P)) return -12;
-  if (up(d_paystart, h_payload_start.data(), 8 * P)) return -12;
-  if (up(d_scanbase, h_scanbase.data(), 8 * P)) return -12;
-  if (up(d_lastsame, h_last_same.data(), P)) return -12;
-  if (up(d_present, h_present.data(), P)) return -12;
-  if (up(d_rstart, h_range_start.data(), 8 * P)) return -12;
-  if (up(d_rlen, h_range_len.data(), 8 * P)) return -12;
+  if (up(d_segstart, L->seg_start.data(), 8 * P)) return -12;
+  if (up(d_body, L->body.data(), 8 * P)) return -12;
+  if (up(d_paystart, L->payload_start.data(), 8 * P)) return -12;
+  if (up(d_scanbase, L->scanbase.data(), 8 * P)) return -12;
+  if (up(d_lastsame, L->last_same.data(), P)) return -12;
+  if (up(d_present, L->present.data(), P)) return -12;
+  if (up(d_rstart, L->range_start.data(), 8 * P)) return -12;
+  if (up(d_rlen, L->range_len.data(), 8 * P)) return -12;
+  L->d_segstart = (const uint64_t*)d_segstart.p;
+  L->d_body = (const uint64_t*)d_body.p;
+  L->d_paystart = (const uint64_t*)d_paystart.p;
+  L->d_scanbase = (const uint64_t*)d_scanbase.p;
+  L->d_lastsame = (const uint8_t*)d_lastsame.p;
+  L->d_present = (const uint8_t*)d_present.p;
+  L->d_rstart = (const uint64_t*)d_rstart.p;
+  L->d_rlen = (const uint64_t*)d_rlen.p;
+  return 0;
+}
 
-  /* 6. emit records */
-  static int force_simple = -1;
-  if (force_simple < 0) force_simple = getenv("TZS_EMIT_SIMPLE") ? 1 : 0;
-  /* k_emit_uniform (lane-per-record word moves) measured SLOWER than the
-   * half-wave path: each store instruction scatters 64 partial-line writes
-   * across 64 records and write coalescing collapses (37 ms vs 10 ms at C2).
-   * Kept behind TZS_EMIT_UNIFORM=1 for experiments; default off. */
-  static int no_uniform_emit = -1;
-  if (no_uniform_emit < 0) {
-    const char* e = getenv("TZS_EMIT_UNIFORM");
-    no_uniform_emit = (e && e[0] == '1') ? 0 : 1;
-  }
-  if (arith_emit) {
-    /* force_simple falls through inside the kernel (no desc/scan exist) */
+/* (f) emit the records.  uni (nullable) selects the arithmetic emit:
+ * single-segment uniform records, no RLE — src/dst are pure arithmetic and
+ * no descriptors or size scan exist.  Everything else takes k_emit_records. */
+static void launch_emit(tzs_sorter* s, const RecSet& v, const UniformEmit* uni,
+                        const EmitLayout& L) {
+  const uint32_t n = v.n;
+  if (uni)
     hipLaunchKernelGGL(k_emit_uniform_arith, dim3(grid_waves(n)), dim3(BLOCK),
-                       0, 0, rt.data0, d_idx,
-                       (const uint32_t*)s->parts_sorted.p,
-                       (const uint64_t*)d_pstart.p,
-                       (const uint64_t*)d_paystart.p, d_out, n, uni_rec,
-                       uh_len, uh_word);
-  } else if (!no_uniform_emit && !force_simple && uni_rec && no_same &&
-      uni_rec % 8 == 0 && uni_rec <= 16 * 8) {
-    hipLaunchKernelGGL((k_emit_uniform<uint64_t, 16>), dim3(grid1d(n)), dim3(BLOCK),
-                       0, 0, (const RecDesc*)descbuf.p, (const uint64_t*)s->scan.p,
-                       (const uint32_t*)s->parts_sorted.p, (const uint64_t*)d_paystart.p,
-                       (const uint64_t*)d_scanbase.p, d_out, n, uh_len, uh_word, uni_rec);
-  } else if (!no_uniform_emit && !force_simple && uni_rec && no_same &&
-             uni_rec % 4 == 0 && uni_rec <= 32 * 4) {
-    hipLaunchKernelGGL((k_emit_uniform<uint32_t, 32>), dim3(grid1d(n)), dim3(BLOCK),
-                       0, 0, (const RecDesc*)descbuf.p, (const uint64_t*)s->scan.p,
-                       (const uint32_t*)s->parts_sorted.p, (const uint64_t*)d_paystart.p,
-                       (const uint64_t*)d_scanbase.p, d_out, n, uh_len, uh_word, uni_rec);
-  } else {
-    /* k_emit_span (LDS span image + dense aligned stores) measured 29-32 ms
-       vs 10.3 ms at C2 — the per-lane staging loops and LDS round trip cost
-       more than the wide stores save; L2 already merges the byte path's
-       consecutive stores.  Kept for experiments under TZS_EMIT_SPAN=1. */
-    static int use_span = -1;
-    if (use_span < 0) {
-      const char* e = getenv("TZS_EMIT_SPAN");
-      use_span = (e && e[0] == '1') ? 1 : 0;
-    }
-    static int use_v2 = -1;
-    if (use_v2 < 0) {
-      const char* e = getenv("TZS_EMIT_V2");
-      /* measured SLOWER (emit 10.2 -> 28.7 ms at C2): the 64-record LDS
-         drain serializes on shuffle+bank-conflicted byte reads; kept for
-         experiments only */
-      use_v2 = (e && e[0] == '1') ? 1 : 0;
-    }
-    if (use_v2 && !force_simple && !use_span) {
-      hipLaunchKernelGGL(k_emit_records_v2, dim3(grid_waves(n)), dim3(BLOCK), 0, 0,
-                         (const RecDesc*)descbuf.p,
-                         (const uint8_t*)s->same.p, (const uint64_t*)s->scan.p,
-                         (const uint32_t*)s->parts_sorted.p,
-                         (const uint64_t*)d_paystart.p,
-                         (const uint64_t*)d_scanbase.p, d_out, n);
-    } else if (use_span && !force_simple) {
-      hipLaunchKernelGGL(k_emit_span, dim3(grid_waves(n)), dim3(BLOCK), 0, 0,
-                         (const RecDesc*)descbuf.p,
-                         (const uint8_t*)s->same.p, (const uint64_t*)s->scan.p,
-                         (const uint32_t*)s->parts_sorted.p,
-                         (const uint64_t*)d_paystart.p,
-                         (const uint64_t*)d_scanbase.p, d_out, n);
-    } else {
-      hipLaunchKernelGGL(k_emit_records, dim3(grid_waves(n)), dim3(BLOCK), 0, 0,
-                         (const RecDesc*)descbuf.p,
-                         (const uint8_t*)s->same.p, (const uint64_t*)s->scan.p,
-                         (const uint32_t*)s->parts_sorted.p,
-                         (const uint64_t*)d_paystart.p,
-                         (const uint64_t*)d_scanbase.p, d_out, n, force_simple);
-    }
-  }
-  (void)hipEventRecord(ev[5]);
+                       0, 0, v.rt.data0, (const uint32_t*)s->sidx.p,
+                       (const uint32_t*)s->parts_sorted.p, L.d_pstart,
+                       L.d_paystart, L.d_out, n, uni->rec, uni->hdr_len,
+                       uni->hdr_word);
+  else
+    hipLaunchKernelGGL(k_emit_records, dim3(grid_waves(n)), dim3(BLOCK), 0, 0,
+                       L.d_desc, (const uint8_t*)s->same.p,
+                       (const uint64_t*)s->scan.p,
+                       (const uint32_t*)s->parts_sorted.p, L.d_paystart,
+                       L.d_scanbase, L.d_out, n);
+}
 
-  /* 7. CRC of every present segment's payload..EOF range */
+/* (g) segment headers, EOF markers and the CRC32 trailer of every present
+ * segment's payload..EOF range; returns with the device idle */
+static int patch_and_crc(const EmitLayout& L, int P) {
+  static thread_local DBuf d_partcrc;
   if (d_partcrc.alloc(4 * P)) return -12;
   /* patch headers + EOF BEFORE crc (crc covers payload..EOF) */
   hipLaunchKernelGGL(k_patch_segments, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0,
-                     d_out, (const uint64_t*)d_segstart.p, (const uint64_t*)d_body.p,
-                     (const uint8_t*)d_lastsame.p, (const uint32_t*)d_partcrc.p,
-                     (const uint8_t*)d_present.p, P);
-  rc = crc_ranges_launch(d_out, (const uint64_t*)d_rstart.p,
-                         (const uint64_t*)d_rlen.p, h_range_len.data(), P,
-                         (uint32_t*)d_partcrc.p);
+                     L.d_out, L.d_segstart, L.d_body, L.d_lastsame,
+                     (const uint32_t*)d_partcrc.p, L.d_present, P);
+  int rc = crc_ranges_launch(L.d_out, L.d_rstart, L.d_rlen, L.range_len.data(), P,
+                             (uint32_t*)d_partcrc.p);
   if (rc) return rc;
   /* re-patch to write CRC trailers (header/EOF rewrite is idempotent) */
   hipLaunchKernelGGL(k_patch_segments, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0,
-                     d_out, (const uint64_t*)d_segstart.p, (const uint64_t*)d_body.p,
-                     (const uint8_t*)d_lastsame.p, (const uint32_t*)d_partcrc.p,
-                     (const uint8_t*)d_present.p, P);
+                     L.d_out, L.d_segstart, L.d_body, L.d_lastsame,
+                     (const uint32_t*)d_partcrc.p, L.d_present, P);
   HIP_CHECK(hipDeviceSynchronize());
-  (void)hipEventRecord(ev[6]);
-  (void)hipEventSynchronize(ev[6]);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ev[2], ev[3]); T.sort_ns += (int64_t)(ms * 1e6);
-  (void)hipEventElapsedTime(&ms, ev[4], ev[5]); T.emit_ns += (int64_t)(ms * 1e6);
-  (void)hipEventElapsedTime(&ms, ev[5], ev[6]); T.crc_ns += (int64_t)(ms * 1e6);
-  (void)hipEventElapsedTime(&ms, ev[2], ev[6]); T.total_ns += (int64_t)(ms * 1e6);
+  return 0;
+}
+
+/* s->skey = masked composites in final base-sort order, s->sidx = global
+ * record ids.  Entered from sort_and_emit (base radix sort) or from the
+ * flush merge path (k_merge_path2 tree over retained spill orders, which
+ * also passes the merged lo keys as d_lo). */
+static int refine_and_emit(tzs_sorter* s, std::vector<SegDesc> hsegs,
+                           std::vector<uint32_t> hbase, RecTable rt, uint32_t n,
+                           const SortParams& prm, const uint8_t* h_spill_rle,
+                           int nspills_rle, SpillData* outsp, bool apply_combine,
+                           SpillData* retain, const uint64_t* d_lo) {
+  tzs_times& T = s->times;
+  enum { EV_BEGIN, EV_REFINED, EV_LAYOUT, EV_EMITTED, EV_DONE, EV_COUNT };
+  Events<EV_COUNT> ev;
+  ev.create(EV_COUNT);
+  const int P = s->conf.num_partitions;
+  const int c0 = refine_start_byte(prm, s->pbits);
+  const bool will_combine = apply_combine && s->conf.combiner == 1;
+  RecSet v{rt, n, std::move(hsegs), std::move(hbase)};
+  int rc = 0;
+  ev.record(EV_BEGIN);
+
+  Refined ref;
+  rc = refine_levels(s, v, prm.ser_mode, c0, d_lo, retain && !will_combine,
+                     ev.ev[EV_REFINED], &ref);
+  if (rc) return rc;
+  radix_release_temps(); /* dead from here, like the level scratch */
+
+  if (retain && !will_combine) {
+    rc = retain_sorted_order(s, v.rt, v.n, prm, c0, ref.lk0_ready, retain);
+    if (rc) return rc;
+  }
+
+  int writer_rle = 0;
+  rc = decide_writer_rle(s, v.rt, v.n, ref.neq, h_spill_rle, nspills_rle, &writer_rle);
+  if (rc) return rc;
+
+  s->combine_applied = false;
+  if (will_combine) {
+    rc = combine_fold(s, &v, prm, c0, retain);
+    if (rc) return rc;
+    writer_rle = 0; /* folded keys are unique; rle never triggers */
+  } else {
+    s->combined_parts_valid = false;
+  }
+
+  rc = writer_same_flags(s, v.rt, v.n, writer_rle, h_spill_rle, nspills_rle);
+  if (rc) return rc;
+  const bool no_same = (writer_rle == 0) &&
+      (ref.neq == 0 || (nspills_rle == 1 && h_spill_rle && !h_spill_rle[0]));
+  const UniformEmit uni = uniform_emit_gate(v, s->combine_applied, no_same);
+  /* single-segment uniform no-RLE: src/dst/sizes are pure arithmetic — skip
+     the descriptor build, the size scan AND the per-partition scan gather */
+  const UniformEmit* arith = (v.rt.nspills == 1 && uni.rec) ? &uni : nullptr;
+
+  EmitLayout L;
+  uint64_t total_body = 0;
+  if (arith) total_body = (uint64_t)v.n * (uni.hdr_len + uni.rec);
+  else if ((rc = emit_sizes(s, v, &L.d_desc, &total_body))) return rc;
+  s->skey.release();  /* composites are dead once parts_sorted exists */
+  rc = partition_layout(s, v, ref.meta, arith, total_body, outsp, &L);
+  if (rc) return rc;
+  outsp->rle = (uint8_t)writer_rle;
+  ev.record(EV_LAYOUT);
+  if ((rc = upload_layout(&L))) return rc;
+
+  launch_emit(s, v, arith, L);
+  ev.record(EV_EMITTED);
+
+  if ((rc = patch_and_crc(L, P))) return rc;
+  ev.record(EV_DONE);
+  (void)hipEventSynchronize(ev.ev[EV_DONE]);
+  T.sort_ns += ev.ns(EV_BEGIN, EV_REFINED);
+  T.emit_ns += ev.ns(EV_LAYOUT, EV_EMITTED);
+  T.crc_ns += ev.ns(EV_EMITTED, EV_DONE);
+  T.total_ns += ev.ns(EV_BEGIN, EV_DONE);
   T.dominant_kernel_ns += g_scatter_ns;
   T.sort_passes += g_scatter_launches;  /* scatter launch count (roofline) */
   T.dominant_kernel_elems += g_scatter_elems;
-  for (auto& e : ev) (void)hipEventDestroy(e);
   return 0;
+}
+
+/* ---- the core: sort current buffer + emit IFile segments ---- */
+static int sort_and_emit(tzs_sorter* s, HostRT& hrt, uint32_t n,
+                         const int32_t* d_part_unsorted,
+                         const uint8_t* h_spill_rle, int nspills_rle,
+                         SpillData* outsp, bool apply_combine = false,
+                         SpillData* retain = nullptr) {
+  tzs_times& T = s->times;
+  g_scatter_ns = 0; g_scatter_launches = 0; g_scatter_elems = 0;
+  Events<3> ev;
+  ev.create(3);
+  ev.record(0);
+
+  RecTable rt = hrt.rt;
+  int P = s->conf.num_partitions;
+  int pbits = s->pbits;
+  SortParams prm = derive_sort_params(s, hrt.segs, n);
+  int ser_mode = prm.ser_mode, SB = prm.SB;
+  /* 1. composites */
+  if (s->skey.alloc(sizeof(uint64_t) * n)) return -12;
+  if (s->sidx.alloc(sizeof(uint32_t) * n)) return -12;
+  uint64_t* d_key = (uint64_t*)s->skey.p;
+  uint32_t* d_idx = (uint32_t*)s->sidx.p;
+  if (ser_mode == 0 && stream_uniform_gate(rt)) {
+#define TZS_CS_LAUNCH(NV)                                                     \
+  case NV:                                                                    \
+    hipLaunchKernelGGL((k_build_composite_stream<NV>), dim3(grid1d(n)),       \
+                       dim3(BLOCK), (BLOCK / WAVE) * NV * WAVE * 16, 0,       \
+                       rt.data0, d_part_unsorted, P, pbits, SB, rt.rec_u0,    \
+                       rt.klen_u0 - 4, d_key, d_idx, n);                      \
+    break;
+    switch ((rt.rec_u0 + 15) / 16) {
+      TZS_CS_LAUNCH(1) TZS_CS_LAUNCH(2) TZS_CS_LAUNCH(3) TZS_CS_LAUNCH(4)
+      TZS_CS_LAUNCH(5) TZS_CS_LAUNCH(6) TZS_CS_LAUNCH(7) TZS_CS_LAUNCH(8)
+    }
+#undef TZS_CS_LAUNCH
+  } else
+    hipLaunchKernelGGL(k_build_composite2, dim3(grid1d(n)), dim3(BLOCK), 0, 0, rt,
+                       d_part_unsorted, P, pbits, prm.ref_pb, SB, ser_mode, d_key,
+                       d_idx, n);
+  ev.record(1);
+
+  /* 2. base radix sort over the top SB bytes of the composite */
+  int rc = radix_sort<uint64_t>(d_key, d_idx, nullptr, n, 8, 8 - SB,
+                                &s->skey, &s->sidx, nullptr);
+  if (rc) return rc;
+  ev.record(2);
+  (void)hipEventSynchronize(ev.ev[2]);
+  T.composite_ns += ev.ns(0, 1);
+  T.sort_ns += ev.ns(1, 2);
+  T.total_ns += ev.ns(0, 2);
+  return refine_and_emit(s, hrt.segs, hrt.base, rt, n, prm, h_spill_rle,
+                         nspills_rle, outsp, apply_combine, retain, nullptr);
 }
 
 __global__ void k_max_u32(const uint32_t* a, uint32_t n, uint32_t* out) {
@@ -5402,8 +4954,8 @@ extern "C" int tzs_sorter_flush(tzs_sorter* s) {
   bool all_sorted = true;
   for (auto* sp : live)
     if (!sp->sorted_valid) all_sorted = false;
-  static int force_resort = -1;
-  if (force_resort < 0) force_resort = getenv("TZS_MERGE_RESORT") ? 1 : 0;
+  static int force_resort_c = -1;
+  const bool force_resort = env_switch("TZS_MERGE_RESORT", ENV_SET, &force_resort_c);
   SpillData finalsp;
   if (!all_sorted || force_resort) {
     /* fallback: stable radix re-sort of the union (round-1 path).  It
@@ -5427,10 +4979,10 @@ extern "C" int tzs_sorter_flush(tzs_sorter* s) {
     for (auto* sp : live)
       if (sp->sort_sb < SBc) SBc = sp->sort_sb;
     uint64_t mask_c = (SBc >= 8) ? ~0ull : ~0ull << (8 * (8 - SBc));
+    prm.ser_mode = common_ser;
+    prm.SB = SBc;
     /* common refinement start for the lo keys */
-    int c0c = common_ser ? (8 * SBc - s->pbits - prm.proxy_w) / 8
-                         : (8 * SBc - s->pbits) / 8;
-    if (c0c < 0) c0c = 0;
+    const int c0c = refine_start_byte(prm, s->pbits);
     /* spills whose retained composites used the content form must be
        rebuilt in serialized form when any spill needs it (their sorted
        order is unchanged: content order == serialized order for the
@@ -5587,7 +5139,7 @@ extern "C" int tzs_sorter_flush(tzs_sorter* s) {
     s->times.merge_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
         std::chrono::steady_clock::now() - t0).count();
     rc = refine_and_emit(s, hrt.segs, hrt.base, hrt.rt, (uint32_t)total_n,
-                         SBc, common_ser, spill_rle.data(), lsp, &finalsp,
+                         prm, spill_rle.data(), lsp, &finalsp,
                          combine_at_merge, nullptr,
                          (const uint64_t*)s->skey_lo.p);
     if (rc) return rc;
@@ -6028,7 +5580,7 @@ extern "C" int tzs_sorter_add_sorted_segment(tzs_sorter* s, const void* d_data,
     uint64_t res[4];
     HIP_CHECK(hipMemcpy(res, mm.p, 32, hipMemcpyDeviceToHost));
     bool uni = (res[0] == res[1]) && (res[2] == res[3]) && res[0] <= 0xFFFFFFFFull;
-    if (getenv("TZS_NO_UNIFORM")) uni = false;
+    if (env_switch("TZS_NO_UNIFORM", ENV_SET)) uni = false;
     sp->rec_u = uni ? (uint32_t)res[0] : 0;
     sp->klen_u = uni ? (uint32_t)res[2] : 0;
   }
@@ -6061,18 +5613,13 @@ extern "C" int tzs_sorter_add_sorted_segment(tzs_sorter* s, const void* d_data,
     }
   }
   {
-    int c0 = prm.ser_mode ? (8 * prm.SB - s->pbits - prm.proxy_w) / 8
-                          : (8 * prm.SB - s->pbits) / 8;
-    if (c0 < 0) c0 = 0;
+    const int c0 = refine_start_byte(prm, s->pbits);
     if (sp->skey2.alloc(8ull * n)) { delete sp; return -12; }
     hipLaunchKernelGGL(k_build_lkeys, dim3(grid1d(n)), dim3(BLOCK), 0, 0,
                        one.rt, c0, 0, prm.ser_mode, (uint64_t*)sp->skey2.p,
                        (uint32_t)n);
-    sp->lo_c0 = c0;
+    mark_sorted_retained(sp, prm, c0);
   }
-  sp->sort_sb = prm.SB;
-  sp->sort_ser_mode = prm.ser_mode;
-  sp->sorted_valid = 1;
   if (d_part) s->have_explicit_parts = true;
   s->spills.push_back(sp);
   s->ctr.output_records += n;
